@@ -16,7 +16,12 @@ brawler (8 KiB of integer state per session, one wavefront per session),
 same session count and rollback shape; its snapshot ring (4 GiB at 65,536
 sessions) does not fit any cache, so it is the HBM-bound line.
 
-Prints ONE JSON line (rank 0).
+A plain run sets up, warms up, times --steps ticks and prints ONE JSON line
+(rank 0).  --dump-outputs DIR also writes what the timed path left after its
+last tick (dump_outputs).  Everything else the benchmark measures, each a run
+of its own outside the timed region, is behind --full: the CPU baselines, the
+live-play (one tick per call) block and the device copy bandwidth next to the
+roofline figures.
 """
 import argparse
 import json
@@ -153,7 +158,7 @@ def cpu_baseline(args, P):
 def measured_copy_gbps(dev, nbytes=1 << 30, iters=10):
     """Device-to-device copy bandwidth (read + write bytes / time) of a 1 GiB
     buffer: the STREAM-copy ceiling SURVEY.md 8(d) asks to report next to the
-    8 TB/s spec peak.  Runs outside every timed region."""
+    8 TB/s spec peak.  Runs outside every timed region, with --full only."""
     import torch
     a = torch.empty(nbytes // 4, dtype=torch.int32, device=dev)
     b = torch.empty_like(a)
@@ -167,6 +172,40 @@ def measured_copy_gbps(dev, nbytes=1 << 30, iters=10):
     gbps = 2 * nbytes * iters / (e0.elapsed_time(e1) / 1e3) / 1e9
     del a, b
     return gbps
+
+
+DUMP_BUDGET_BYTES = 32 << 20  # --dump-outputs: all files together, well inside 64 MB
+
+
+def dump_outputs(path, game, P, images, per_session, seed):
+    """--dump-outputs: what the timed path left after its last tick, as path/<name>.npy.
+    `images` is the [S, state_bytes] u8 live state a caller reads back (read_live) and
+    `per_session` maps further names to [S] integer arrays.  ex_game's image is split into
+    its f32 fields (float32: positions, velocities, rotations) and its frame; any other
+    game's image is written as its 32-bit words.  Integers are written as float64, which
+    holds every 32-bit value and every 16-bit checksum of the bench games exactly.  When
+    all sessions would pass DUMP_BUDGET_BYTES, every array keeps the same sample of
+    sessions, drawn with the run's seed; sessions.npy holds their indices."""
+    import numpy as np
+
+    from ggrs_amd.session import decode_ex_game
+    S, B = images.shape
+    row = (P * 5 * 4 + 8 if game == "ex_game" else B // 4 * 8) + 8 * (len(per_session) + 1)
+    keep = np.arange(S)
+    if S * row > DUMP_BUDGET_BYTES:
+        keep = np.sort(np.random.default_rng(seed).choice(S, DUMP_BUDGET_BYTES // row, replace=False))
+    images = np.ascontiguousarray(images[keep])
+    out = {"sessions": keep}
+    if game == "ex_game":
+        d = decode_ex_game(images, P)
+        out.update({k: d[k] for k in ("frame", "positions", "velocities", "rotations")})
+    else:
+        out["state_words"] = images[:, :B // 4 * 4].view(np.int32)
+    out.update({k: np.asarray(v)[keep] for k, v in per_session.items()})
+    os.makedirs(path, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(path, name + ".npy"),
+                np.ascontiguousarray(a, dtype=np.float32 if a.dtype == np.float32 else np.float64))
 
 
 P2P_ONLY_SOURCES = ("p2p.hpp", "p2p_engine.hip", "wire.hip")
@@ -288,7 +327,8 @@ def roofline_block(bytes_per_launch, avg_kernel_s, ticks_per_launch, launches, k
     when no PMC profile of this configuration is committed, or when the profile's traffic
     over this kernel time would exceed the fastest rate DRAM was measured to take (the copy
     `copy_gbps` or the calibrated store-only ceiling): counters that describe other launches
-    than the ones timed here are refused, not reported."""
+    than the ones timed here are refused, not reported.  `copy_gbps` is measured with --full
+    only; without it that rate is the calibrated store-only ceiling."""
     achieved = bytes_per_launch / avg_kernel_s / 1e9
     r = {"bound": "unprofiled", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
          "frac": achieved / HBM_PEAK_GBS, "frac_basis": "algorithmic bytes / kernel time / 8 TB/s HBM spec",
@@ -595,6 +635,10 @@ def bench_p2p(args):
         kernel_ms, launches = sess.profile_take()
         spans = sess.launch_clock_read(2 * args.steps) if timing == "clock" else None
     a1 = sess.totals()
+    if args.dump_outputs and rank == 0:
+        cur, confirmed = sess.frames()
+        dump_outputs(args.dump_outputs, args.game, P, sess.read_live(),
+                     {"current_frame": cur, "confirmed_frame": confirmed}, args.seed)
     adv, saves, loads, selects, branch = (a1[i] - a0[i] for i in range(5))
     thr, unexpected, panics = sess.counters()
     tot = torch.tensor([adv, saves, loads, panics, selects, branch], dtype=torch.float64, device=dev)
@@ -657,7 +701,7 @@ def bench_p2p(args):
                                                             else (" (one tick per launch)" if tl == 1 else
                                                                   " (fused P2P ticks)")),
                                   pmc_profile(cfg_key, fan_state), "algorithmic: cells loaded/saved, inputs, deliveries",
-                                  measured_copy_gbps(dev))
+                                  measured_copy_gbps(dev) if args.full else None)
         roofline.update(timer)
         write_meta(config_key=cfg_key, source_id=source_id(), fanout_state=fan_state, kernel="p2p_kernel",
                    clock_spans_us=spans, dispatch_overhead_us=timer.get("dispatch_overhead_us"),
@@ -699,7 +743,7 @@ def bench_p2p(args):
             "roofline": roofline,
             "cpu_baseline": None,
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             # the reference rollback path (the oracle's P2PSession + ex_game, reference allocation
             # pattern) on the same arrays: same inputs, same delivery schedule, same rollbacks
             from oracle import oracle as O
@@ -726,6 +770,14 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=400)
     ap.add_argument("--warmup", type=int, default=32)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run what the headline figure does not need, each a run of "
+                         "its own: the CPU baselines (unless --no-cpu-baseline), the live-play block "
+                         "(--realtime-ticks) and the device copy bandwidth of the roofline block")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the timed path left after its last step to DIR/<name>.npy "
+                         "(float32 / float64; the sessions' live state and per-session frames and checksums, rank "
+                         "0's shard; a seeded sample of the sessions when they would pass 32 MB)")
     ap.add_argument("--sessions-per-gpu", type=int, default=None,
                     help="default: 65,536 at --gpus 1 (BASELINE configs[1]), 131,072 at --gpus N > 1 "
                          "(configs[4]: 1,048,576 sessions over 8 GPUs)")
@@ -739,13 +791,13 @@ def main():
     ap.add_argument("--ticks-per-launch", type=int, default=50,
                     help="steady-state ticks fused into one steady_kernel launch (rb_run_ticks call)")
     ap.add_argument("--realtime-ticks", type=int, default=64,
-                    help="after the timed region, this many ticks of one rb_run_ticks call each (live play, "
+                    help="--full: after the timed region, this many ticks of one rb_run_ticks call each (live play, "
                          "inputs arriving per tick): the line's realtime / headroom_60hz fields; 0 = skip")
     ap.add_argument("--game", choices=["ex_game", "brawler"], default="ex_game",
                     help="ex_game = BASELINE configs[1] (default); brawler = configs[2]")
     ap.add_argument("--cpu-sessions", type=int, default=None)
     ap.add_argument("--cpu-ticks", type=int, default=None)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without its CPU baseline legs")
     ap.add_argument("--block-size", type=int, default=0)
     ap.add_argument("--session", choices=["synctest", "p2p"], default="synctest",
                     help="synctest = the headline (BASELINE configs[1]); p2p = P2PSession rollback batches "
@@ -814,7 +866,8 @@ def main():
     # always run untimed, before the W requested warmup ticks, so the timed region is steady state
     # and the warmup has run the fused steady kernel at least once.
     warm = cd + 1 + args.warmup
-    RT = args.realtime_ticks  # one-tick-per-call ticks after the timed region (the 60 Hz serving path)
+    # one-tick-per-call ticks after the timed region (the 60 Hz serving path): with --full only
+    RT = args.realtime_ticks if args.full else 0
     # Kernel timing (GGRS_BENCH_EVENTS).  "clock" (default): every timed launch records its own first
     # wave start and last wave end on the chip's 100 MHz constant clock (rb_launch_clock_*; two plain
     # stores per wave, nothing on the stream or the host inside the timed region), and the kernel time
@@ -976,6 +1029,11 @@ def main():
         spans = sess.launch_clock_read(len(timed_plan)) if clocked else None
         sess.profile_enable(False)
         gather_ms = [a.elapsed_time(b) for a, b in gather_ev]
+        if args.dump_outputs and rank == 0:  # (before the live-play ticks below advance the batch)
+            img, dcs, dfr = sess.read_live()
+            dump_outputs(args.dump_outputs, args.game, P, img[:S],
+                         {"display_checksum": dcs[:S], "display_frame": dfr[:S],
+                          "mismatch_frame": sess.mismatches()[:S]}, args.seed)
         # The 60 Hz serving path, after (outside) the timed region: inputs arrive one tick at a
         # time (ex_game_synctest.rs:50-61), so each tick is its own call and launch.
         rt = None
@@ -1071,7 +1129,7 @@ def main():
         tl = int(round(ticks_per_launch))
         cfg_key = f"{args.game} P={P} cd={cd} W={args.max_prediction} d={args.input_delay} S={S}" + (
             f" tpl={tl}" if tl != 50 else "")
-        copy_gbps = measured_copy_gbps(dev)
+        copy_gbps = measured_copy_gbps(dev) if args.full else None
         roofline = roofline_block(bytes_per_launch, avg_kernel_s, ticks_per_launch, launches,
                                   ((f"steady_kernel<Brawler<{P}>,{cd}>" if brawler else
                                     f"steady_kernel<ExGame<{P},true>,{cd}>") +
@@ -1144,7 +1202,7 @@ def main():
                                       "live play (realtime block)"},
             "cpu_baseline": None,
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(args, P)
         print(json.dumps(line), flush=True)
     sess.close()

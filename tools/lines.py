@@ -108,7 +108,8 @@ def bench(tag, names):
         os.environ.pop(k, None)
     for n in names:
         out = os.path.join(ROOT, "gpurun_out", f"bench_{tag}_{n}")
-        rc = run(["python3", "-u", "bench.py"] + LINES[n][0].split(), out + ".log", 900)
+        # --full: a line carries its CPU baseline, live-play block and measured copy bandwidth
+        rc = run(["python3", "-u", "bench.py", "--full"] + LINES[n][0].split(), out + ".log", 900)
         rows = [l for l in open(out + ".log") if l.startswith("{")]
         with open(out + ".jsonl", "w") as f:
             f.writelines(rows)
