@@ -42,6 +42,9 @@ RB_P2P_FLAG_FANOUT_PER_PLAYER = 32
 RB_GAME_PLUGIN_BASE = 1000
 RB_P2P_REPORTS_PER_TAKE = 8
 RB_P2P_EVENTS_KEPT = 16
+RB_P2P_EXPORT_OK = 0
+RB_P2P_EXPORT_OVERRUN = 1
+SPECTATOR_BUFFER_SIZE = 60  # p2p_spectator_session.rs:16
 
 
 class RbConfig(ctypes.Structure):
@@ -79,6 +82,20 @@ class RbP2PConfig(ctypes.Structure):
         ("fanout_candidates", ctypes.c_int32),
         ("fanout_min_select_permille", ctypes.c_uint32),
         ("reserved", ctypes.c_uint32 * 1),
+    ]
+
+
+class RbSpectatorConfig(ctypes.Structure):
+    _fields_ = [
+        ("abi_version", ctypes.c_int32),
+        ("game", ctypes.c_int32),
+        ("num_sessions", ctypes.c_int32),
+        ("num_players", ctypes.c_int32),
+        ("device", ctypes.c_int32),
+        ("max_frames_behind", ctypes.c_int32),
+        ("catchup_speed", ctypes.c_int32),
+        ("block_size", ctypes.c_uint32),
+        ("reserved", ctypes.c_uint32 * 4),
     ]
 
 
@@ -151,10 +168,26 @@ SIGNATURES = [
     ("rb_p2p_read_desync_events", _I32, [_P, _P, _P, _P, _P, _P]),
     ("rb_p2p_debug_corrupt", _I32, [_P, _I32, _I32, ctypes.c_uint32]),
     ("rb_p2p_receive_peer_connect_status", _I32, [_P, _I32, _P, _P]),
+    ("rb_p2p_export_confirmed_inputs", _I32, [_P, _P, _I32, _P, _P, _P]),
+    ("rb_p2p_read_export_status", _I32, [_P, _P, _P]),
     ("rb_p2p_profile_enable", _I32, [_P, _I32]),
     ("rb_p2p_profile_take", _I32, [_P, ctypes.POINTER(ctypes.c_double), _PI32]),
     ("rb_p2p_launch_clock_arm", _I32, [_P, _I32]),
     ("rb_p2p_launch_clock_read", _I32, [_P, _PU64, _I32, _PI32]),
+    ("rb_spectator_config_init", None, [ctypes.POINTER(RbSpectatorConfig)]),
+    ("rb_spectator_create", _I32, [ctypes.POINTER(RbSpectatorConfig), ctypes.POINTER(_P)]),
+    ("rb_spectator_destroy", None, [_P]),
+    ("rb_spectator_last_error", ctypes.c_char_p, [_P]),
+    ("rb_spectator_set_stream", _I32, [_P, _P]),
+    ("rb_spectator_get_stream", _P, [_P]),
+    ("rb_spectator_receive_host_status", _I32, [_P, _P, _P]),
+    ("rb_spectator_run_ticks", _I32, [_P, _I32, _P, _P, _I32]),
+    ("rb_spectator_read_status", _I32, [_P, _P, _P]),
+    ("rb_spectator_read_frames", _I32, [_P, _P, _P]),
+    ("rb_spectator_read_live", _I32, [_P, _P, _P]),
+    ("rb_spectator_totals", _I32, [_P, _P]),
+    ("rb_spectator_state_bytes", _I32, [_P]),
+    ("rb_spectator_input_bytes", _I32, [_P]),
     ("rb_decode_input_packets", _I32, [_I32, _P, _I32, _I32, _I32, _I32, _I32, _P, ctypes.c_int64, _P, _P, _P, _I32,
                                         _P, _P]),
     ("rb_encode_input_packets", _I32, [_I32, _P, _I32, _I32, _I32, _I32, _P, _I32, _I32, _P, _P, _P, ctypes.c_int64,

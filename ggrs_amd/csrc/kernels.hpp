@@ -838,6 +838,7 @@ __global__ void report_kernel(const typename G::CS* __restrict__ cs, const int32
 
 }  // namespace rb
 #include "p2p.hpp"  // P2PSession kernel (uses load_words / store_words above)
+#include "spectator.hpp"  // SpectatorSession kernel (likewise)
 namespace rb {
 
 // Kernel timing (rb_profile_enable / rb_p2p_profile_enable): the events a launch
@@ -935,6 +936,8 @@ struct GameOps {
   bool fanout_supported = false;
   bool inlane_fanout = false;  // p2p_kernel runs the fan-out itself (inlane_fan), unless fan_generic
   uint32_t input_alphabet = 0;  // InputAlphabet<G>: the per-player fan-out needs all of it as candidates
+  // SpectatorSession ticks (spectator.hpp); the last virtual: RB_PLUGIN_ABI 8
+  virtual hipError_t launch_spectator(const SpectatorParams& p, int block, hipStream_t st) const = 0;
 };
 
 template <class G>
@@ -1110,6 +1113,11 @@ struct GameOpsT final : GameOps {
     } else {
       return hipErrorNotSupported;
     }
+  }
+  hipError_t launch_spectator(const SpectatorParams& p, int block, hipStream_t st) const override {
+    const int grid = (p.Spad * G::kLanes + block - 1) / block;
+    hipLaunchKernelGGL(spectator_kernel<G>, dim3(grid), dim3(block), 0, st, p);
+    return hipGetLastError();
   }
 };
 

@@ -39,6 +39,7 @@ struct rb_p2p {
   uint8_t* disc_mask = nullptr;       // [S] device copy of rb_p2p_disconnect_player's session mask
   DesyncParams ds{};                  // desync detection buffers (desync_interval > 0)
   PeerParams peer{};                  // peers' connect-status reports (RB_P2P_FLAG_PEER_STATUS)
+  int32_t* exp_state = nullptr;       // [2][Spad]: next_spectator_frame, export status (rb_p2p_export_confirmed_inputs)
   bool prof = false;
   std::vector<std::pair<hipEvent_t, hipEvent_t>> prof_ev;
   size_t prof_used = 0;
@@ -95,6 +96,7 @@ void free_all(rb_p2p* b) {
   if (b->fan.ev) (void)hipEventDestroy(b->fan.ev);
   if (b->peer.last) (void)hipFree(b->peer.last);
   if (b->peer.disc) (void)hipFree(b->peer.disc);
+  if (b->exp_state) (void)hipFree(b->exp_state);
   for (auto& pr : b->prof_ev) {
     (void)hipEventDestroy(pr.first);
     (void)hipEventDestroy(pr.second);
@@ -204,6 +206,58 @@ __global__ void p2p_peer_status_kernel(PeerParams pp, const int32_t* __restrict_
     const size_t o = (static_cast<size_t>(e) * 4 + static_cast<size_t>(i)) * Spad + s;
     pp.last[o] = max(pp.last[o], last[static_cast<size_t>(i) * S + s]);
     pp.disc[o] = pp.disc[o] | (disc[static_cast<size_t>(i) * S + s] ? 1 : 0);
+  }
+}
+
+// send_confirmed_inputs_to_spectators (p2p_session.rs:676-703) over confirmed_inputs
+// (sync_layer.rs:203-217), one thread per session, on the bookkeeping rows and the input ring as the
+// last launch left them (include/ggrs_amd.h rb_p2p_export_confirmed_inputs).
+template <int IB>
+__global__ void p2p_export_kernel(const int32_t* __restrict__ qs, const uint8_t* __restrict__ ring,
+                                  const int32_t* __restrict__ status, int32_t* __restrict__ exp_state, int S, int Spad,
+                                  int P, uint8_t* __restrict__ out, int32_t frames, int32_t* __restrict__ upto,
+                                  int32_t* __restrict__ last_frames, uint8_t* __restrict__ disconnected) {
+  const int s = blockIdx.x * blockDim.x + threadIdx.x;
+  if (s >= S) return;
+  const size_t sp = static_cast<size_t>(Spad);
+  const int32_t cur = qs[QS_CUR * sp + s];
+  int32_t conn[4];
+  bool disc[4];
+  int32_t confirmed = INT32_MAX, newest = kNullFrame;  // confirmed_frame (:487-498); the newest frame any queue holds
+  for (int h = 0; h < P; ++h) {  // the packed rows, behind the escape bit the absolute ones (q_unpack)
+    uint32_t w[4];
+    int32_t ab[7] = {0, 0, 0, 0, 0, 0, 0};
+    for (int i = 0; i < 4; ++i) w[i] = static_cast<uint32_t>(qs[(QS_PLAYER0 + (QF_LA_CONN + i) * 4 + h) * sp + s]);
+    if (w[3] & kQmEsc)
+      for (int i = 0; i < 7; ++i) ab[i] = qs[(QS_PLAYER0 + (QF_ABS0 + i) * 4 + h) * sp + s];
+    const QFields f = q_unpack(w, cur, ab);
+    conn[h] = f.conn;
+    disc[h] = f.disc;
+    if (!f.disc) confirmed = min(confirmed, f.conn);
+    newest = max(newest, f.la);
+  }
+  int32_t next = exp_state[s], est = exp_state[sp + s];
+  // a slot the session still had to send was overwritten: frame `next` shares its slot with
+  // next + 128.  Sticky, and a word of its own (the panic word and the ticks are untouched).
+  if (newest != kNullFrame && newest - next >= kQueueLen) est = RB_P2P_EXPORT_OVERRUN;
+  if (est == RB_P2P_EXPORT_OK && status[s] != kP2PStatusPanic) {
+    while (next <= confirmed && next < frames) {
+      for (int h = 0; h < P; ++h) {
+        const size_t src = (static_cast<size_t>(next & (kQueueLen - 1)) * P + h) * sp + s;
+        const size_t dst = (static_cast<size_t>(next) * P + h) * S + s;
+        const bool blank = disc[h] && conn[h] < next;  // PlayerInput::blank_input (sync_layer.rs:210-211)
+        if constexpr (IB == 4) reinterpret_cast<uint32_t*>(out)[dst] = blank ? 0u : reinterpret_cast<const uint32_t*>(ring)[src];
+        else out[dst] = blank ? uint8_t{0} : ring[src];
+      }
+      ++next;
+    }
+  }
+  exp_state[s] = next;
+  exp_state[sp + s] = est;
+  upto[s] = next - 1;  // RB_NULL_FRAME while nothing is exported
+  for (int h = 0; h < P; ++h) {  // local_connect_status: the Input message's peer_connect_status
+    last_frames[static_cast<size_t>(h) * S + s] = conn[h];
+    disconnected[static_cast<size_t>(h) * S + s] = disc[h] ? 1 : 0;
   }
 }
 
@@ -860,6 +914,43 @@ rb_status rb_p2p_receive_peer_connect_status(rb_p2p* b, int32_t endpoint, const 
   hipLaunchKernelGGL(p2p_peer_status_kernel, dim3((b->S + 255) / 256), dim3(256), 0, b->stream, b->peer, last_frames,
                      disconnected, b->S, b->Spad, b->P, endpoint);
   P2P_TRY(b, hipGetLastError());
+  return RB_OK;
+}
+
+rb_status rb_p2p_export_confirmed_inputs(rb_p2p* b, void* inputs_by_frame, int32_t frames, int32_t* upto,
+                                         int32_t* last_frames, uint8_t* disconnected) {
+  if (!inputs_by_frame || !upto || !last_frames || !disconnected || frames <= 0)
+    return pfail(b, RB_INVALID_REQUEST, "rb_p2p_export_confirmed_inputs: missing output tensor");
+  DeviceScope dev_scope(b->device);
+  if (!b->exp_state) {  // next_spectator_frame = 0 (p2p_session.rs:201), status OK
+    P2P_TRY(b, hipMalloc(&b->exp_state, 2 * static_cast<size_t>(b->Spad) * 4));
+    P2P_TRY(b, hipMemsetAsync(b->exp_state, 0, 2 * static_cast<size_t>(b->Spad) * 4, b->stream));
+  }
+  const dim3 grid((b->S + 255) / 256), block(256);
+  auto k = b->ops->input_bytes == 4 ? p2p_export_kernel<4> : p2p_export_kernel<1>;
+  if (b->ops->input_bytes != 4 && b->ops->input_bytes != 1)
+    return pfail(b, RB_INVALID_REQUEST, "rb_p2p_export_confirmed_inputs: 1- and 4-byte inputs");
+  hipLaunchKernelGGL(k, grid, block, 0, b->stream, b->qs, static_cast<const uint8_t*>(b->ring), b->status, b->exp_state,
+                     b->S, b->Spad, b->P, static_cast<uint8_t*>(inputs_by_frame), frames, upto, last_frames, disconnected);
+  P2P_TRY(b, hipGetLastError());
+  return RB_OK;
+}
+
+rb_status rb_p2p_read_export_status(rb_p2p* b, int32_t* status, int32_t* next_frame) {
+  if (!b->exp_state) {  // no export yet
+    for (int s = 0; s < b->S; ++s) {
+      if (status) status[s] = RB_P2P_EXPORT_OK;
+      if (next_frame) next_frame[s] = 0;
+    }
+    return RB_OK;
+  }
+  std::vector<int32_t> st;
+  rb_status r = read_rows(b, b->exp_state, 2, st);
+  if (r != RB_OK) return r;
+  for (int s = 0; s < b->S; ++s) {
+    if (next_frame) next_frame[s] = st[s];
+    if (status) status[s] = st[static_cast<size_t>(b->Spad) + s];
+  }
   return RB_OK;
 }
 

@@ -7,8 +7,8 @@
 // ggrs_amd.plugin.build_game_plugin).  rb_register_game_plugin (engine.hip)
 // dlopens the library and creates the game's GameOps through
 // rb_plugin_make_ops: every kernel of the engine (SyncTest ticks, fused steady
-// ticks, P2P ticks, checksum reports) is instantiated here for the game, so
-// the plugin's own code object carries them.
+// ticks, P2P ticks, spectator ticks, checksum reports) is instantiated here
+// for the game, so the plugin's own code object carries them.
 #include "../../include/ggrs_amd_game.hpp"
 #include "kernels.hpp"
 

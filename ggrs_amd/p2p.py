@@ -21,7 +21,7 @@ from .session import DeviceError, InvalidRequest, Panic, _StreamOrdered, input_d
 from .synth import SEED, splitmix64
 
 
-class PlayerType(enum.Enum):  # lib.rs:115-124 (Spectator is not part of the batch)
+class PlayerType(enum.Enum):  # lib.rs:115-124 (spectators are batches of their own: ggrs_amd.spectator)
     Local = "local"
     Remote = "remote"
 
@@ -286,6 +286,39 @@ class P2PSession(_StreamOrdered):
         if st == L.RB_INVALID_REQUEST:
             raise InvalidRequest((self._lib.rb_p2p_last_error(self._h) or b"").decode())
         self._check(st)
+
+    # -- the spectators' feed (p2p_session.rs:303, 676-703)
+    def export_confirmed_inputs(self, inputs_by_frame, upto, last_frames, disconnected) -> None:
+        """send_confirmed_inputs_to_spectators for every session, between run_ticks calls:
+        every frame up to the minimum last_frame of the connected players that was not
+        exported before is written to inputs_by_frame [F, P, S] (Input values, absolute
+        frames, all players; zero for a disconnected player past its last frame), then
+        upto [S] int32 (newest frame exported so far, NULL_FRAME: none), last_frames [P, S]
+        int32 and disconnected [P, S] uint8 (the host's connect status).  CUDA tensors,
+        written in place; what SpectatorSession.run_ticks / receive_host_status read."""
+        import torch
+        P, S = self.num_players, self.num_sessions
+        assert tuple(inputs_by_frame.shape[1:]) == (P, S) and inputs_by_frame.is_contiguous()
+        assert inputs_by_frame.element_size() == np.dtype(self.input_dtype).itemsize
+        assert tuple(upto.shape) == (S,) and upto.dtype == torch.int32 and upto.is_contiguous()
+        assert tuple(last_frames.shape) == (P, S) and last_frames.dtype == torch.int32 and last_frames.is_contiguous()
+        assert tuple(disconnected.shape) == (P, S) and disconnected.dtype == torch.uint8 and disconnected.is_contiguous()
+        ptrs = [_dev_ptr(x)[0] for x in (inputs_by_frame, upto, last_frames, disconnected)]
+        cur = self._pre()
+        st = self._lib.rb_p2p_export_confirmed_inputs(self._h, ptrs[0], int(inputs_by_frame.shape[0]), ptrs[1], ptrs[2],
+                                                      ptrs[3])
+        self._post(cur, (inputs_by_frame, upto, last_frames, disconnected), outputs=True)
+        self._check(st)
+
+    def export_status(self):
+        """(status [S]: RB_P2P_EXPORT_OK, or RB_P2P_EXPORT_OVERRUN for a session whose input
+        ring overwrote frames it still had to export (it exports nothing more);
+        next_spectator_frame [S])."""
+        st = np.empty(self.num_sessions, np.int32)
+        nx = np.empty(self.num_sessions, np.int32)
+        self._check(self._lib.rb_p2p_read_export_status(self._h, st.ctypes.data_as(ctypes.c_void_p),
+                                                        nx.ctypes.data_as(ctypes.c_void_p)))
+        return st, nx
 
     def debug_corrupt(self, session: int, word: int, xor_mask: int) -> None:
         """Flip canonical state word `word` of the live state and every cell of `session`."""

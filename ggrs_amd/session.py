@@ -331,6 +331,45 @@ class SessionBuilder:
             raise InvalidRequest(msg) if st == L.RB_INVALID_REQUEST else DeviceError(msg)
         return P2PSession(lib, h, game_of(pc.game), pc)
 
+    # -- spectators (builder.rs:210-244, 310-334)
+    def with_max_frames_behind(self, max_frames_behind: int) -> "SessionBuilder":  # :210-225
+        if max_frames_behind < 1:
+            raise InvalidRequest("Max frames behind cannot be smaller than 1.")
+        if max_frames_behind >= L.SPECTATOR_BUFFER_SIZE:
+            raise InvalidRequest("Max frames behind cannot be larger or equal than the Spectator buffer size (60)")
+        self._max_frames_behind = int(max_frames_behind)
+        return self
+
+    def with_catchup_speed(self, catchup_speed: int) -> "SessionBuilder":  # :229-244
+        """Checked against the max_frames_behind set so far (default 10), like the reference."""
+        if catchup_speed < 1:
+            raise InvalidRequest("Catchup speed cannot be smaller than 1.")
+        if catchup_speed >= getattr(self, "_max_frames_behind", 10):
+            raise InvalidRequest("Catchup speed cannot be larger or equal than the allowed maximum frames behind host")
+        self._catchup_speed = int(catchup_speed)
+        return self
+
+    def start_spectator_session(self) -> "SpectatorSession":  # :310-334
+        """A batch of spectators of num_players-player host sessions; they start Running (the
+        handshake is the network's).  The create call checks the final values again."""
+        from .spectator import SpectatorSession
+        sc = L.RbSpectatorConfig()
+        lib = L.load()
+        lib.rb_spectator_config_init(ctypes.byref(sc))
+        sc.game = self._cfg.game
+        sc.num_sessions = self._cfg.num_sessions
+        sc.num_players = self._cfg.num_players
+        sc.device = self._cfg.device
+        sc.max_frames_behind = getattr(self, "_max_frames_behind", sc.max_frames_behind)
+        sc.catchup_speed = getattr(self, "_catchup_speed", sc.catchup_speed)
+        sc.block_size = self._cfg.block_size
+        h = ctypes.c_void_p()
+        st = lib.rb_spectator_create(ctypes.byref(sc), ctypes.byref(h))
+        if st != L.RB_OK:
+            msg = (lib.rb_spectator_last_error(None) or b"").decode()
+            raise InvalidRequest(msg) if st == L.RB_INVALID_REQUEST else DeviceError(msg)
+        return SpectatorSession(lib, h, game_of(sc.game), sc)
+
     def start_synctest_session(self) -> "SyncTestSession":  # :342-354
         lib = L.load()
         h = ctypes.c_void_p()

@@ -259,7 +259,9 @@ rb_status rb_launch_clock_read(rb_batch* b, uint64_t* start_end, int32_t cap, in
  * remote inputs roll sessions back individually (per-session depth), on the
  * device.  rb_p2p_disconnect_player covers disconnects the user issues;
  * peer-reported disconnects arrive through rb_p2p_receive_peer_connect_status
- * (RB_P2P_FLAG_PEER_STATUS, below).  Spectators and time sync are out of scope.
+ * (RB_P2P_FLAG_PEER_STATUS, below).  Spectators are batches of their own
+ * (rb_spectator_*, below), fed by rb_p2p_export_confirmed_inputs; registering
+ * them on the host (PlayerType::Spectator) and time sync are out of scope.
  * ======================================================================== */
 typedef struct rb_p2p rb_p2p;
 
@@ -472,6 +474,48 @@ rb_status rb_p2p_read_desync_events(rb_p2p* b, uint32_t* counts, int32_t* frames
 rb_status rb_p2p_receive_peer_connect_status(rb_p2p* b, int32_t endpoint, const int32_t* last_frames,
                                              const uint8_t* disconnected);
 
+/* P2PSession::send_confirmed_inputs_to_spectators (p2p_session.rs:303, 676-703)
+ * over SyncLayer::confirmed_inputs (sync_layer.rs:203-217), batched: the feed of
+ * a spectator batch (rb_spectator_run_ticks).  Device pointers, stream ordered,
+ * called between rb_p2p_run_ticks calls.  Per session, with confirmed = the
+ * minimum of ConnectionStatus::last_frame over the players that are not
+ * disconnected (confirmed_frame, p2p_session.rs:487-498; not the SyncLayer's
+ * clamped last_confirmed_frame): while next_spectator_frame <= confirmed and
+ * next_spectator_frame < frames, every player's input of that frame goes to
+ *   inputs_by_frame [frames][num_players][S] Input values (the layout and
+ *                   absolute frames of rb_p2p_run_ticks's remote_inputs):
+ *                   zero for a player with disconnected && last_frame < frame,
+ *                   else the InputQueue's entry of the frame
+ * and next_spectator_frame (per session, 0 at first: p2p_session.rs:201) moves
+ * on.  Then
+ *   upto            int32 [S]: the newest frame exported so far (RB_NULL_FRAME: none)
+ *   last_frames     int32 [num_players][S], disconnected uint8 [num_players][S]:
+ *                   the host's local_connect_status, the peer_connect_status
+ *                   its Input messages carry (rb_spectator_receive_host_status)
+ * Nothing is written past upto.  Panicked sessions export nothing.
+ *
+ * The reference sends after every tick, so it never reads an InputQueue slot
+ * that a later frame has overwritten.  Here a caller may export rarely: a
+ * session in which any queue has added a frame >= next_spectator_frame + 128
+ * (the ring holds 128 frames) has lost inputs it still had to send; it exports
+ * nothing more, from that call on, and reports RB_P2P_EXPORT_OVERRUN through
+ * rb_p2p_read_export_status.  That status is a word of its own: the sticky
+ * panic word, rb_p2p_read_status and the session's ticks are untouched.
+ *
+ * Called after every tick the export equals the reference's per-tick sending.
+ * After longer launches it equals it too, except with RB_P2P_FLAG_PEER_STATUS
+ * when a peer-reported disconnect lands inside a launch: frames between the
+ * player's last frame and the tick it was disconnected in, which the
+ * reference had already sent with the player's inputs, are exported zeroed. */
+#define RB_P2P_EXPORT_OK 0
+#define RB_P2P_EXPORT_OVERRUN 1
+rb_status rb_p2p_export_confirmed_inputs(rb_p2p* b, void* inputs_by_frame, int32_t frames, int32_t* upto,
+                                         int32_t* last_frames, uint8_t* disconnected);
+/* Per session: RB_P2P_EXPORT_OK / RB_P2P_EXPORT_OVERRUN and next_spectator_frame
+ * (both as the last export left them; before the first: OK and 0).  Either
+ * pointer may be NULL.  Synchronises. */
+rb_status rb_p2p_read_export_status(rb_p2p* b, int32_t* status, int32_t* next_frame);
+
 /* Fault injection for tests (ex_game.rs:211-215 trigger_desync, generalised):
  * XOR `xor_mask` into canonical state word `word` of `session`'s live state
  * and of every cell it holds (checksums unchanged), between ticks. */
@@ -484,6 +528,101 @@ rb_status rb_p2p_profile_take(rb_p2p* b, double* total_ms, int32_t* launches);
  * with the two-launch fan-out every fanout_kernel launch, takes a slot. */
 rb_status rb_p2p_launch_clock_arm(rb_p2p* b, int32_t launches);
 rb_status rb_p2p_launch_clock_read(rb_p2p* b, uint64_t* start_end, int32_t cap, int32_t* launches);
+
+/* ===========================================================================
+ * SpectatorSession batches (sessions/p2p_spectator_session.rs) — rollback-free
+ * replicas of host sessions.
+ *
+ * S independent spectators, each following one host session: a spectator
+ * advances only on inputs the host has confirmed and sent
+ * (rb_p2p_export_confirmed_inputs), one frame per tick, or catchup_speed
+ * frames while it is more than max_frames_behind frames behind
+ * (p2p_spectator_session.rs:109-139).  As for the P2P batches the network
+ * layer is the caller's: per tick it passes the newest frame the host's Input
+ * messages have delivered and the inputs by frame; the host's connect status
+ * goes through rb_spectator_receive_host_status.  Time sync,
+ * WaitRecommendation, NetworkStats and the handshake are out of scope: the
+ * sessions start Running.
+ *
+ * A spectator's state after frame c is bit-identical to the cell the host
+ * saved for frame c + 1 once that frame is confirmed, and rb_spectator_read_live
+ * returns it with that cell's checksum.
+ * ======================================================================== */
+typedef struct rb_spectator rb_spectator;
+
+typedef struct rb_spectator_config {
+  int32_t abi_version;       /* = RB_ABI_VERSION */
+  int32_t game;              /* rb_game, as rb_p2p_config.game */
+  int32_t num_sessions;
+  int32_t num_players;       /* with_num_players (builder.rs:154-157): the host's */
+  int32_t device;
+  int32_t max_frames_behind; /* with_max_frames_behind (builder.rs:210-225), default 10 */
+  int32_t catchup_speed;     /* with_catchup_speed (builder.rs:229-244), default 1 */
+  uint32_t block_size;
+  uint32_t reserved[4];
+} rb_spectator_config;
+
+/* SessionBuilder::new() defaults (builder.rs:13, 23-25): 2 players, 10 frames behind, catch-up speed 1. */
+void rb_spectator_config_init(rb_spectator_config* cfg);
+
+/* SessionBuilder::start_spectator_session (builder.rs:310-334) for S sessions
+ * that start Running.  Validated before any device work, on the final values,
+ * RB_INVALID_REQUEST with the reference's messages (rb_spectator_last_error(NULL)):
+ * "Max frames behind cannot be smaller than 1.", "Max frames behind cannot be
+ * larger or equal than the Spectator buffer size (60)", "Catchup speed cannot
+ * be smaller than 1.", "Catchup speed cannot be larger or equal than the
+ * allowed maximum frames behind host"; then the game and player-count rules
+ * of rb_p2p_create. */
+rb_status rb_spectator_create(const rb_spectator_config* cfg, rb_spectator** out);
+void rb_spectator_destroy(rb_spectator* b);
+const char* rb_spectator_last_error(const rb_spectator* b);
+rb_status rb_spectator_set_stream(rb_spectator* b, void* hip_stream);
+void* rb_spectator_get_stream(const rb_spectator* b); /* as rb_get_stream */
+
+/* The host's connect status as its Input messages carry it (handle_event's
+ * Event::Input, p2p_spectator_session.rs:243-245, over UdpProtocol::on_input's
+ * merge, protocol.rs:629-636): last_frames int32 [num_players][S] and
+ * disconnected uint8 [num_players][S], device memory (what
+ * rb_p2p_export_confirmed_inputs writes); the stored status becomes
+ * (stored.disconnected || reported, max(stored.last_frame, reported)).
+ * Stream ordered before the next launch. */
+rb_status rb_spectator_receive_host_status(rb_spectator* b, const int32_t* last_frames, const uint8_t* disconnected);
+
+/* n_ticks x SpectatorSession::advance_frame (+ handle_requests) for every
+ * session, in ONE device launch.  Device pointers, stream ordered:
+ *   host_upto   int32 [n_ticks][S]: the newest frame delivered before tick t's
+ *               advance_frame (RB_NULL_FRAME: none yet; a value below the
+ *               session's last_recv_frame changes nothing; a value >= frames
+ *               counts as frames - 1)
+ *   host_inputs [frames][num_players][S] Input values by frame, complete up to
+ *               the largest host_upto of the call
+ * Per tick and session: last_recv_frame = max(last_recv_frame, host_upto); then
+ * one frame, or catchup_speed frames when last_recv_frame - current_frame >
+ * max_frames_behind.  A session whose next frame has not arrived does not
+ * advance (RB_PREDICTION_THRESHOLD); one whose next frame left the 60-frame
+ * spectator buffer (last_recv_frame >= frame + 60) never advances again
+ * (RB_SPECTATOR_TOO_FAR_BEHIND).  A player the host status reports
+ * disconnected before the frame advances as (zeroed, Disconnected). */
+rb_status rb_spectator_run_ticks(rb_spectator* b, int32_t n_ticks, const int32_t* host_upto, const void* host_inputs,
+                                 int32_t frames);
+
+/* Per session, the last tick: its rb_status (RB_OK, RB_PREDICTION_THRESHOLD,
+ * RB_SPECTATOR_TOO_FAR_BEHIND) and AdvanceFrame count (-1 before the first
+ * tick).  Either pointer may be NULL.  Synchronises. */
+rb_status rb_spectator_read_status(rb_spectator* b, int32_t* status, int32_t* n_advance);
+/* current_frame and last_recv_frame per session (RB_NULL_FRAME at first,
+ * p2p_spectator_session.rs:67-68); frames_behind_host (:80-84) is their difference.  Synchronises. */
+rb_status rb_spectator_read_frames(rb_spectator* b, int32_t* current, int32_t* last_recv);
+/* The game state after frame current_frame, images [S][rb_spectator_state_bytes]
+ * (frame word = current_frame + 1), and checksums [S][2] (lo, hi): the
+ * checksum of the host's cell of frame current_frame + 1 (every launch stores
+ * it; zero before the first).  Either may be NULL.  Synchronises. */
+rb_status rb_spectator_read_live(rb_spectator* b, void* images, uint64_t* checksums);
+/* Since create: [0] AdvanceFrames executed, [1] ticks that returned
+ * PredictionThreshold, [2] ticks that returned SpectatorTooFarBehind (summed over sessions). */
+rb_status rb_spectator_totals(rb_spectator* b, uint64_t* out3);
+int32_t rb_spectator_state_bytes(const rb_spectator* b);
+int32_t rb_spectator_input_bytes(const rb_spectator* b);
 
 /* ===========================================================================
  * Batched input packets (network/compression.rs): one

@@ -56,7 +56,8 @@
 
 /* ABI of the plugin entry points (rb_plugin_abi); bump when the engine's
  * kernel parameter structs or the layout of the state they point to change
- * (7: the packed P2P bookkeeping rows). */
-#define RB_PLUGIN_ABI 7
+ * (7: the packed P2P bookkeeping rows; 8: the spectator launcher, a new
+ * last virtual of the game's launcher table). */
+#define RB_PLUGIN_ABI 8
 
 #endif /* GGRS_AMD_GAME_HPP */

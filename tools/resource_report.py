@@ -1,7 +1,7 @@
 """Register and scratch use of every kernel of the product build (the compiler's own report,
 -Rpass-analysis=kernel-resource-usage, on the Makefile's flags), one line per kernel.
 
-    python3 tools/resource_report.py > profiles/r06_resource_usage.txt
+    python3 tools/resource_report.py > profiles/spectator_resource_usage.txt
 """
 import os
 import re
