@@ -42,6 +42,7 @@ RB_P2P_FLAG_FANOUT_PER_PLAYER = 32
 RB_GAME_PLUGIN_BASE = 1000
 RB_P2P_REPORTS_PER_TAKE = 8
 RB_P2P_EVENTS_KEPT = 16
+RB_P2P_WAIT_EVENTS_KEPT = 8
 RB_P2P_EXPORT_OK = 0
 RB_P2P_EXPORT_OVERRUN = 1
 SPECTATOR_BUFFER_SIZE = 60  # p2p_spectator_session.rs:16
@@ -170,6 +171,13 @@ SIGNATURES = [
     ("rb_p2p_receive_peer_connect_status", _I32, [_P, _I32, _P, _P]),
     ("rb_p2p_export_confirmed_inputs", _I32, [_P, _P, _I32, _P, _P, _P]),
     ("rb_p2p_read_export_status", _I32, [_P, _P, _P]),
+    ("rb_p2p_time_sync_enable", _I32, [_P, _I32]),
+    ("rb_p2p_receive_quality", _I32, [_P, _I32, _P, _P]),
+    ("rb_p2p_export_time_sync", _I32, [_P, _P, _P]),
+    ("rb_p2p_read_time_sync", _I32, [_P, _P, _P, _P, _P]),
+    ("rb_p2p_read_wait_recommendations", _I32, [_P, _P, _P, _P]),
+    ("rb_p2p_debug_read_time_sync_windows", _I32, [_P, _P]),
+    ("rb_debug_time_sync_average", _I32, [_I32, _P, _P, _P, ctypes.c_int64]),
     ("rb_p2p_profile_enable", _I32, [_P, _I32]),
     ("rb_p2p_profile_take", _I32, [_P, ctypes.POINTER(ctypes.c_double), _PI32]),
     ("rb_p2p_launch_clock_arm", _I32, [_P, _I32]),

@@ -45,6 +45,7 @@ struct Plugin {
   std::string path;
   void* handle;
   GameOps* (*make)(int32_t, int32_t);
+  bool tick_log;  // rb_plugin_tick_log: its P2P kernels write the time-sync tick log
 };
 std::mutex g_plugins_mu;
 std::vector<Plugin> g_plugins;
@@ -55,6 +56,12 @@ std::unique_ptr<GameOps> make_plugin_ops(int game, int players) {
   const int k = game - RB_GAME_PLUGIN_BASE;
   if (k < 0 || k >= static_cast<int>(g_plugins.size())) return nullptr;
   return std::unique_ptr<GameOps>(g_plugins[static_cast<size_t>(k)].make(players, RB_PLUGIN_ABI));
+}
+
+bool plugin_writes_tick_log(int game) {
+  std::lock_guard<std::mutex> lk(g_plugins_mu);
+  const int k = game - RB_GAME_PLUGIN_BASE;
+  return k >= 0 && k < static_cast<int>(g_plugins.size()) && g_plugins[static_cast<size_t>(k)].tick_log;
 }
 }  // namespace rb
 
@@ -296,7 +303,8 @@ rb_status rb_register_game_plugin(const char* path, int32_t* game_id) {
     dlclose(h);
     return fail(nullptr, RB_INVALID_REQUEST, "not a game plugin of this engine (rb_plugin_abi / rb_plugin_make_ops)");
   }
-  g_plugins.push_back(Plugin{path, h, make});
+  auto tick_log = reinterpret_cast<int32_t (*)()>(dlsym(h, "rb_plugin_tick_log"));
+  g_plugins.push_back(Plugin{path, h, make, tick_log && tick_log() == 1});
   *game_id = RB_GAME_PLUGIN_BASE + static_cast<int32_t>(g_plugins.size() - 1);
   return RB_OK;
 }

@@ -1015,7 +1015,7 @@ struct GameOpsT final : GameOps {
                        reinterpret_cast<rb_checksum_report*>(out));
     return hipGetLastError();
   }
-  template <bool kSpec, bool kSparse, bool kNet, bool kMtf = false>
+  template <bool kSpec, bool kSparse, bool kNet, bool kMtf = false, bool kLog = false>
   static hipError_t launch_p2p_as_m(const P2PParams& p, int grid, int block, hipStream_t st, const LaunchEv& ev) {
     size_t lds = p2p_lds_bytes<G>(block);  // (the HBM-cell launches below)
     if constexpr ((!kSpec || inlane_fan<G>()) && !kNet && p2p_lds_queue<G>()) {
@@ -1031,8 +1031,8 @@ struct GameOpsT final : GameOps {
           !(kHasQ && p.many_waves)) {
         // lane-asynchronous ticks (plain path and sparse saving) unless the batch asked for lock-step
         // ticks; the fan-out runs lock-step ticks
-        auto k = (!p.sync_ticks && !kSpec) ? p2p_kernel<G, kSpec, kSparse, kNet, true, !kSpec, false, kMtf>
-                                           : p2p_kernel<G, kSpec, kSparse, kNet, true, false, false, kMtf>;
+        auto k = (!p.sync_ticks && !kSpec) ? p2p_kernel<G, kSpec, kSparse, kNet, true, !kSpec, false, kMtf, false, false, kLog>
+                                           : p2p_kernel<G, kSpec, kSparse, kNet, true, false, false, kMtf, false, false, kLog>;
         lds = p2p_lds_bytes<G, true>(block) + p2p_lds_cell_bytes<G>(block, p.W);
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize,
                                            static_cast<int>(lds));
@@ -1042,7 +1042,7 @@ struct GameOpsT final : GameOps {
     }
     if constexpr ((!kSpec || (RB_SPEC_Q && inlane_fan<G>())) && !kNet && p2p_lds_queue<G>() && G::kLanes > 1) {
       if (p.T >= kLdsQMinTicks && (!kSpec || (p.many_waves && !p.fan_generic))) {  // the input ring alone in LDS
-        auto k = p2p_kernel<G, kSpec, kSparse, kNet, false, false, false, kMtf, true>;
+        auto k = p2p_kernel<G, kSpec, kSparse, kNet, false, false, false, kMtf, true, false, kLog>;
         lds = p2p_lds_bytes<G, true>(block);
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize,
                                            static_cast<int>(lds));
@@ -1054,23 +1054,30 @@ struct GameOpsT final : GameOps {
     // SGPR spills; 9.70 -> 9.59 us at 65,536 sessions, packet-fed 11.07 -> 10.45; r06_ab_one_tick.log)
     if constexpr (!kSpec && !kNet) {
       if (p.T == 1)
-        return rb_launch(p2p_kernel<G, kSpec, kSparse, kNet, false, false, false, kMtf, false, true>, dim3(grid),
+        return rb_launch(p2p_kernel<G, kSpec, kSparse, kNet, false, false, false, kMtf, false, true, kLog>, dim3(grid),
                          dim3(block), static_cast<uint32_t>(lds), st, ev, p);
     }
-    return rb_launch(p2p_kernel<G, kSpec, kSparse, kNet, false, false, false, kMtf>, dim3(grid), dim3(block),
+    return rb_launch(p2p_kernel<G, kSpec, kSparse, kNet, false, false, false, kMtf, false, false, kLog>, dim3(grid), dim3(block),
                      static_cast<uint32_t>(lds), st, ev, p);
   }
   // the fan-out's candidates: the alphabet itself when it has at most K values, else the queues'
   // move-to-front lists (kMtf); ex_game (16 inputs) builds both, larger alphabets only the lists
-  template <bool kSpec, bool kSparse, bool kNet>
-  static hipError_t launch_p2p_as(const P2PParams& p, int grid, int block, hipStream_t st, const LaunchEv& ev) {
+  template <bool kSpec, bool kSparse, bool kNet, bool kLog>
+  static hipError_t launch_p2p_as_l(const P2PParams& p, int grid, int block, hipStream_t st, const LaunchEv& ev) {
     if constexpr (kSpec) {
       if constexpr (InputAlphabet<G>::value > static_cast<uint32_t>(kSpecBranches))
-        return launch_p2p_as_m<kSpec, kSparse, kNet, true>(p, grid, block, st, ev);
+        return launch_p2p_as_m<kSpec, kSparse, kNet, true, kLog>(p, grid, block, st, ev);
       else if (InputAlphabet<G>::value > static_cast<uint32_t>(p.fan_k))
-        return launch_p2p_as_m<kSpec, kSparse, kNet, true>(p, grid, block, st, ev);
+        return launch_p2p_as_m<kSpec, kSparse, kNet, true, kLog>(p, grid, block, st, ev);
     }
-    return launch_p2p_as_m<kSpec, kSparse, kNet, false>(p, grid, block, st, ev);
+    return launch_p2p_as_m<kSpec, kSparse, kNet, false, kLog>(p, grid, block, st, ev);
+  }
+  // time sync on (P2PParams::tick_log; never a packet-fed launch, which launch_p2p has taken by
+  // now): the instantiations that write the tick log (p2p_kernel kLog)
+  template <bool kSpec, bool kSparse, bool kNet>
+  static hipError_t launch_p2p_as(const P2PParams& p, int grid, int block, hipStream_t st, const LaunchEv& ev) {
+    if (p.tick_log) return launch_p2p_as_l<kSpec, kSparse, kNet, true>(p, grid, block, st, ev);
+    return launch_p2p_as_l<kSpec, kSparse, kNet, false>(p, grid, block, st, ev);
   }
   hipError_t launch_p2p(const P2PParams& p, int block, hipStream_t st, const LaunchEv& ev) const override {
     const int grid = (p.Spad * G::kLanes + block - 1) / block;
@@ -1128,6 +1135,8 @@ std::unique_ptr<GameOps> make_brawler_ops(int players);
 std::unique_ptr<GameOps> make_stub_ops(int game, int players);
 // a game registered with rb_register_game_plugin (engine.hip); nullptr if unknown
 std::unique_ptr<GameOps> make_plugin_ops(int game, int players);
+// whether that plugin's P2P kernels write the time-sync tick log (built since P2PParams::tick_log)
+bool plugin_writes_tick_log(int game);
 
 inline std::unique_ptr<GameOps> make_game(int game, int players, bool lane_per_session) {
   switch (game) {

@@ -368,6 +368,15 @@ struct PeerParams {
   int32_t on;     // RB_P2P_FLAG_PEER_STATUS
 };
 
+// The tick log's rows (P2PParams::tick_log), one word per session each: current_frame at the
+// tick's entry; how the tick ended (bits 0-1) with the disconnected bits after
+// update_player_disconnects (bits 4-7); the disconnected bits at the tick's entry, written only
+// with peers' connect-status reports on (otherwise they are the other row's).  A row nobody wrote
+// holds kTlUnwritten in kTlEnd: the session had stopped on a panic before that tick.
+constexpr int kTlCur = 0, kTlEnd = 1, kTlEntry = 2, kTlRows = 3;
+constexpr uint32_t kTlOk = 0u, kTlThreshold = 1u, kTlPanic = 2u;
+constexpr int32_t kTlUnwritten = -1;
+
 struct P2PParams {
   uint32_t* snap;
   void* cs;
@@ -421,7 +430,14 @@ struct P2PParams {
   int64_t packet_stride;
   const int32_t* pk_len;
   const int32_t* pk_start;
-  int32_t* pk_status;  // [P][S] the last tick's decode status per endpoint (wire.hip codes), or null
+  // pk_status shares its word with the tick log of rb_p2p_time_sync_enable (time_sync.hpp): packet-fed
+  // launches never log (kWire excludes kLog), and the parameter block keeps its size, which the
+  // network-fed kernels hold a copy of in scratch.  Tick t of session s records at
+  // tick_log[(t * kTlRows + k) * Spad + s] what p2p_time_sync_kernel needs of it (rows kTl*); null: no log.
+  union {
+    int32_t* pk_status;  // [P][S] the last tick's decode status per endpoint (wire.hip codes), or null
+    int32_t* tick_log;
+  };
   int32_t* acks;       // [P][S] after the launch: the newest frame received per endpoint (the ack), or null
   unsigned long long* launch_clock;  // rb_p2p_launch_clock_arm: this launch's [waves][start, end], or null
 };
@@ -876,7 +892,10 @@ __device__ uint64_t rb_p2p_phase[8 * 4096];
   } while (0)
 #endif
 template <class G, bool kSpec, bool kSparse, bool kNet, bool kLdsC, bool kAsync, bool kWire = false, bool kMtf = false,
-          bool kQ = false, bool kOne = false>
+          bool kQ = false, bool kOne = false, bool kLog = false>
+// kLog: the launch writes the tick log (P2PParams::tick_log, time sync on).  A template flag and not
+// a null check: the instantiations without it keep their registers (most sit at their SGPR or VGPR
+// caps, profiles/time_sync_resource_usage.txt).
 // kQ (the input ring alone in LDS, 32 KiB per 256 threads) is capped at 128 VGPRs: with the cells in
 // HBM four workgroups fit a CU, so batches of more than two waves per SIMD run four resident instead
 // of the LDS-cell kernel's two (kernels.hpp launch_p2p_as_m).
@@ -887,6 +906,7 @@ __attribute__((amdgpu_waves_per_eu(kOne ? RB_P2P_ONE_WAVES : (kQ && kSpec) ? RB_
 p2p_kernel(const P2PParams p) {
   static_assert(!kAsync || (kLdsC && !kSpec && !kNet), "lane-asynchronous ticks: plain or sparse path, LDS cells");
   static_assert(!kWire || (!kSpec && !kSparse && !kNet && !kAsync), "packet-fed ticks: the plain lock-step path");
+  static_assert(!(kWire && kLog), "the tick log shares its parameter word with the packet-fed launches' pk_status");
   using InRec = typename G::InRec;
   using CS = typename G::CS;
   constexpr int NW = G::NWL;
@@ -1729,6 +1749,10 @@ p2p_kernel(const P2PParams p) {
     // 4.88 -> 5.26 us, while the plain fused ticks run faster with it (3.37 -> 3.11 us; sparse and the
     // C4 fan-out neutral; profiles/r06_ab_prefetch_branch.log).
     const bool pre_next = (kWire && kLdsC) || T > 1;
+    // the tick log (time_sync.hpp): current_frame as advance_frame finds it (a threshold decision that
+    // ends in a panic may leave `cur` mid-rollback).  Kept in a register until the log's other word
+    // is known: a store here would sit in front of the tick's loads in the memory queue.
+    [[maybe_unused]] const int32_t log_cur = cur;
     if constexpr (kPrefetch) {
       if (pre_next) {
 #pragma unroll
@@ -1807,6 +1831,12 @@ p2p_kernel(const P2PParams p) {
             dsc[h] = q[h].disc;
             lastf[h] = q[h].conn_last;
           }
+        }
+        if (kLog && lead) {  // the tick log: local_connect_status[h].disconnected as the poll saw it
+          uint32_t m = 0u;
+#pragma unroll
+          for (int h = 0; h < P; ++h) m |= (dsc[h] ? 1u : 0u) << h;
+          p.tick_log[(static_cast<size_t>(t) * kTlRows + kTlEntry) * Spad + s] = static_cast<int32_t>(m);
         }
         auto at = [&](int e, int i) { return (static_cast<size_t>(e) * 4 + static_cast<size_t>(i)) * Spad + s; };
 #pragma unroll
@@ -1918,6 +1948,31 @@ p2p_kernel(const P2PParams p) {
         }
       } else {
         threshold = false;
+      }
+    }
+    if constexpr (kLog) {
+      // the tick log: how the tick ends (send_input reached, Err(PredictionThreshold), panic) and
+      // local_connect_status[h].disconnected after update_player_disconnects, what
+      // max_frame_advantage and send_input see.
+      // A row marked kTlOk or kTlThreshold can still end in a panic: rollback_and_save or
+      // run_desync after this point (tick(), the lane-asynchronous loop), and run_desync of a
+      // threshold tick just below.  Such a panic is not recorded here.  p2p_time_sync_kernel infers
+      // it from three things this kernel keeps: the status word is sticky (kP2PStatusPanic), a
+      // panicked session returns before its ticks and so writes no further row, and the time-sync
+      // kernel resets every row it consumed.  The last written row of a session whose status says
+      // panic is then the tick that panicked.  A change to any of the three must record the panic here.
+      uint32_t m = 0u;
+      if (any_disc) {
+#pragma unroll
+        for (int h = 0; h < P; ++h) {
+          if constexpr (kSplit) m |= (group_min<L>(lane == h && q[0].disc ? 0 : 1) == 0 ? 1u : 0u) << h;
+          else m |= (q[h].disc ? 1u : 0u) << h;
+        }
+      }
+      const uint32_t end = status == kP2PStatusPanic ? kTlPanic : threshold ? kTlThreshold : kTlOk;
+      if (lead) {
+        p.tick_log[(static_cast<size_t>(t) * kTlRows + kTlCur) * Spad + s] = log_cur;
+        p.tick_log[(static_cast<size_t>(t) * kTlRows + kTlEnd) * Spad + s] = static_cast<int32_t>(end | m << 4);
       }
     }
     if (status == kP2PStatusPanic) return 0;

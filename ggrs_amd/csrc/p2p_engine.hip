@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "kernels.hpp"
+#include "time_sync.hpp"
 
 using namespace rb;
 
@@ -40,6 +41,11 @@ struct rb_p2p {
   DesyncParams ds{};                  // desync detection buffers (desync_interval > 0)
   PeerParams peer{};                  // peers' connect-status reports (RB_P2P_FLAG_PEER_STATUS)
   int32_t* exp_state = nullptr;       // [2][Spad]: next_spectator_frame, export status (rb_p2p_export_confirmed_inputs)
+  TimeSyncParams ts{};                // rb_p2p_time_sync_enable: the per-session rows and windows (time_sync.hpp)
+  bool ts_on = false;
+  int32_t* ts_log = nullptr;          // [ts_log_ticks][kTlRows][Spad] the tick log, every kTlEnd row unwritten between calls
+  int32_t ts_log_ticks = 0;
+  bool ticked = false;                // a tick has run (rb_p2p_time_sync_enable comes before the first)
   bool prof = false;
   std::vector<std::pair<hipEvent_t, hipEvent_t>> prof_ev;
   size_t prof_used = 0;
@@ -97,6 +103,9 @@ void free_all(rb_p2p* b) {
   if (b->peer.last) (void)hipFree(b->peer.last);
   if (b->peer.disc) (void)hipFree(b->peer.disc);
   if (b->exp_state) (void)hipFree(b->exp_state);
+  if (b->ts.state) (void)hipFree(b->ts.state);
+  if (b->ts.win) (void)hipFree(b->ts.win);
+  if (b->ts_log) (void)hipFree(b->ts_log);
   for (auto& pr : b->prof_ev) {
     (void)hipEventDestroy(pr.first);
     (void)hipEventDestroy(pr.second);
@@ -614,6 +623,34 @@ struct DeviceScope {
 };
 }  // namespace
 
+namespace {
+constexpr const char* kTsOff = "time sync is off (rb_p2p_time_sync_enable)";
+// The tick log for a call of n ticks.  It grows to the largest call seen, and only once the stream
+// is idle: the launches before this call may still read the old one.
+rb_status ts_log_reserve(rb_p2p* b, int32_t n) {
+  if (n <= b->ts_log_ticks) return RB_OK;
+  P2P_TRY(b, hipStreamSynchronize(b->stream));
+  if (b->ts_log) P2P_TRY(b, hipFree(b->ts_log));
+  b->ts_log = nullptr;
+  b->ts_log_ticks = 0;
+  const size_t bytes = static_cast<size_t>(n) * kTlRows * b->Spad * 4;
+  P2P_TRY(b, hipMalloc(&b->ts_log, bytes));
+  P2P_TRY(b, hipMemsetAsync(b->ts_log, 0xff, bytes, b->stream));  // kTlUnwritten
+  b->ts_log_ticks = n;
+  return RB_OK;
+}
+// p2p_time_sync_kernel over the n ticks the P2P launch(es) of this call just logged
+rb_status ts_launch(rb_p2p* b, const P2PParams& p, int32_t n) {
+  const dim3 grid((b->Spad + 255) / 256), block(256);  // lanes past S do nothing
+  auto k = b->P == 1 ? p2p_time_sync_kernel<1> : b->P == 2 ? p2p_time_sync_kernel<2>
+         : b->P == 3 ? p2p_time_sync_kernel<3> : p2p_time_sync_kernel<4>;
+  hipLaunchKernelGGL(k, grid, block, 0, b->stream, b->ts, b->ts_log, static_cast<int64_t>(kTlRows) * b->Spad, p.upto, p.upto_stride, b->status, n,
+                     b->S, b->Spad, p.remote_frames, b->cfg.local_mask, b->cfg.input_delay, b->peer.on);
+  P2P_TRY(b, hipGetLastError());
+  return RB_OK;
+}
+}  // namespace
+
 rb_status rb_p2p_fanout_state(rb_p2p* b, int32_t* active, double* select_fraction, int32_t* windows,
                               int32_t* turned_off) {
   if (!b->fanout) return pfail(b, RB_INVALID_REQUEST, "the batch has no fan-out");
@@ -638,6 +675,12 @@ rb_status rb_p2p_run_ticks(rb_p2p* b, int32_t n_ticks, const void* local_inputs,
   p.remote_frames = remote_frames;
   p.T = n_ticks;
   DeviceScope dev_scope(b->device);
+  if (b->ts_on) {
+    rb_status r = ts_log_reserve(b, n_ticks);
+    if (r != RB_OK) return r;
+    p.tick_log = b->ts_log;
+  }
+  b->ticked = true;
   if (b->fanout) {
     rb_status r = fan_before(b);
     if (r != RB_OK) return r;
@@ -687,6 +730,7 @@ rb_status rb_p2p_run_ticks(rb_p2p* b, int32_t n_ticks, const void* local_inputs,
     for (int32_t t = 0; t < n_ticks && e == hipSuccess; ++t) {
       pt.local_in = p.local_in + static_cast<int64_t>(t) * p.local_stride;
       pt.upto = p.upto + static_cast<int64_t>(t) * p.upto_stride;
+      if (p.tick_log) pt.tick_log = p.tick_log + static_cast<int64_t>(t) * kTlRows * b->Spad;  // this tick's rows
       pt.launch_clock = b->clock.next();
       e = b->ops->launch_p2p(pt, b->block, b->stream);
       fp.launch_clock = b->clock.next();
@@ -696,6 +740,10 @@ rb_status rb_p2p_run_ticks(rb_p2p* b, int32_t n_ticks, const void* local_inputs,
   if (e != hipSuccess) return pfail(b, RB_DEVICE_ERROR, std::string("p2p launch: ") + hipGetErrorString(e));
   if (e1 && !one_launch) P2P_TRY(b, hipEventRecord(e1, b->stream));
   if (e0) ++b->prof_used;  // only a launch that went out has its event pair recorded
+  if (b->ts_on) {
+    rb_status r = ts_launch(b, p, n_ticks);
+    if (r != RB_OK) return r;
+  }
   if (b->fanout) return fan_after(b, n_ticks);
   return RB_OK;
 }
@@ -711,6 +759,8 @@ rb_status rb_p2p_run_ticks_packets(rb_p2p* b, int32_t n_ticks, const void* local
   if (b->cfg.sparse_saving || b->fanout || b->ds.interval > 0 || b->peer.on)
     return pfail(b, RB_INVALID_REQUEST,
                  "rb_p2p_run_ticks_packets: sparse saving, the fan-out and network reports take rb_p2p_run_ticks");
+  if (b->ts_on)  // last_recv_frame is decided inside the kernel there
+    return pfail(b, RB_INVALID_REQUEST, "rb_p2p_run_ticks_packets: time sync takes rb_p2p_run_ticks");
   // a packet's reference input (frame start - 1) may be as old as the newest received frame -
   // 2 * max_prediction (recv_inputs' retain, protocol.rs:684-686); the 128-entry input queue ring
   // holds the newest 128 frames, so that frame must be younger than last - 127
@@ -727,6 +777,7 @@ rb_status rb_p2p_run_ticks_packets(rb_p2p* b, int32_t n_ticks, const void* local
   p.pk_status = decode_status;
   p.acks = acks;
   p.launch_clock = b->clock.next();
+  b->ticked = true;
   DeviceScope dev_scope(b->device);
   LaunchEv ev;  // the kernel's own start / end (hipExtLaunchKernel)
   if (b->prof) {
@@ -952,6 +1003,132 @@ rb_status rb_p2p_read_export_status(rb_p2p* b, int32_t* status, int32_t* next_fr
     if (status) status[s] = st[static_cast<size_t>(b->Spad) + s];
   }
   return RB_OK;
+}
+
+// ---- time sync (time_sync.hpp)
+rb_status rb_p2p_time_sync_enable(rb_p2p* b, int32_t fps) {
+  if (fps <= 0) return pfail(b, RB_INVALID_REQUEST, "FPS should be higher than 0.");  // builder.rs:190-194
+  if (b->ts_on) return pfail(b, RB_INVALID_REQUEST, "rb_p2p_time_sync_enable: time sync is already on");
+  if (b->ticked) return pfail(b, RB_INVALID_REQUEST, "rb_p2p_time_sync_enable: comes before the batch's first tick");
+  if (b->cfg.game >= RB_GAME_PLUGIN_BASE && !plugin_writes_tick_log(b->cfg.game))
+    return pfail(b, RB_INVALID_REQUEST, "rb_p2p_time_sync_enable: rebuild the game plugin against the current headers");
+  DeviceScope dev_scope(b->device);
+  const size_t st = static_cast<size_t>(TS_ROWS) * b->Spad * 4, wn = 2ull * kTsWindow * 4 * b->Spad * 4;
+  int32_t *state = nullptr, *win = nullptr;
+  P2P_TRY(b, hipMalloc(&state, st));
+  if (hipError_t e = hipMalloc(&win, wn); e != hipSuccess) {
+    (void)hipFree(state);
+    return pfail(b, RB_DEVICE_ERROR, std::string("hipMalloc: ") + hipGetErrorString(e));
+  }
+  b->ts.state = state;
+  b->ts.win = win;
+  b->ts.fps = fps;
+  // TimeSync::default, local / remote_frame_advantage 0, round_trip_time 0, next_recommended_sleep 0,
+  // frames_ahead 0, no event
+  P2P_TRY(b, hipMemsetAsync(state, 0, st, b->stream));
+  P2P_TRY(b, hipMemsetAsync(win, 0, wn, b->stream));
+  b->ts_on = true;
+  return RB_OK;
+}
+
+rb_status rb_p2p_receive_quality(rb_p2p* b, int32_t handle, const int32_t* rtt_ms, const int32_t* frame_advantage) {
+  if (!b->ts_on) return pfail(b, RB_INVALID_REQUEST, kTsOff);
+  if (handle < 0 || handle >= b->P || ((b->cfg.local_mask >> handle) & 1u))
+    return pfail(b, RB_INVALID_REQUEST, "quality reports come from a remote handle's endpoint");
+  if (!rtt_ms && !frame_advantage) return RB_OK;
+  DeviceScope dev_scope(b->device);
+  hipLaunchKernelGGL(p2p_receive_quality_kernel, dim3((b->S + 255) / 256), dim3(256), 0, b->stream, b->ts, rtt_ms,
+                     frame_advantage, b->S, b->Spad, handle);
+  P2P_TRY(b, hipGetLastError());
+  return RB_OK;
+}
+
+rb_status rb_p2p_export_time_sync(rb_p2p* b, int32_t* frames_ahead_dev, int32_t* local_adv_dev) {
+  if (!b->ts_on) return pfail(b, RB_INVALID_REQUEST, kTsOff);
+  if (!frames_ahead_dev && !local_adv_dev) return RB_OK;
+  DeviceScope dev_scope(b->device);
+  hipLaunchKernelGGL(p2p_export_time_sync_kernel, dim3((b->S + 255) / 256), dim3(256), 0, b->stream, b->ts,
+                     frames_ahead_dev, local_adv_dev, b->S, b->Spad, b->P);
+  P2P_TRY(b, hipGetLastError());
+  return RB_OK;
+}
+
+rb_status rb_p2p_read_time_sync(rb_p2p* b, int32_t* frames_ahead, int32_t* local_adv, int32_t* remote_adv,
+                                int32_t* rtt_ms) {
+  if (!b->ts_on) return pfail(b, RB_INVALID_REQUEST, kTsOff);
+  DeviceScope dev_scope(b->device);
+  std::vector<int32_t> st;
+  rb_status r = read_rows(b, b->ts.state, TS_ROWS, st);
+  if (r != RB_OK) return r;
+  const size_t Sp = b->Spad;
+  for (int s = 0; s < b->S; ++s) {
+    if (frames_ahead) frames_ahead[s] = st[TS_FRAMES_AHEAD * Sp + s];
+    for (int h = 0; h < b->P; ++h) {
+      const size_t o = static_cast<size_t>(h) * b->S + s;
+      if (local_adv) local_adv[o] = st[(TS_LOCAL_ADV + h) * Sp + s];
+      if (remote_adv) remote_adv[o] = st[(TS_REMOTE_ADV + h) * Sp + s];
+      if (rtt_ms) rtt_ms[o] = st[(TS_RTT + h) * Sp + s];
+    }
+  }
+  return RB_OK;
+}
+
+rb_status rb_p2p_read_wait_recommendations(rb_p2p* b, uint32_t* counts, int32_t* frames, int32_t* skip_frames) {
+  if (!b->ts_on) return pfail(b, RB_INVALID_REQUEST, kTsOff);
+  static_assert(kTsEvents == RB_P2P_WAIT_EVENTS_KEPT, "the event ring of time_sync.hpp");
+  DeviceScope dev_scope(b->device);
+  std::vector<int32_t> st;
+  rb_status r = read_rows(b, b->ts.state, TS_ROWS, st);
+  if (r != RB_OK) return r;
+  const size_t Sp = b->Spad, E = kTsEvents;
+  for (int s = 0; s < b->S; ++s) {
+    const uint32_t cnt = static_cast<uint32_t>(st[TS_EV_N * Sp + s]), kept = cnt < E ? cnt : static_cast<uint32_t>(E);
+    if (counts) counts[s] = cnt;
+    for (size_t e = 0; e < E; ++e) {  // oldest kept first
+      const bool has = e < kept;
+      const size_t q = (cnt - kept + e) % E, o = static_cast<size_t>(s) * E + e;
+      if (frames) frames[o] = has ? st[(TS_EV_FRAME + q) * Sp + s] : kNullFrame;
+      if (skip_frames) skip_frames[o] = has ? st[(TS_EV_SKIP + q) * Sp + s] : 0;
+    }
+  }
+  return RB_OK;
+}
+
+rb_status rb_p2p_debug_read_time_sync_windows(rb_p2p* b, int32_t* out) {
+  if (!b->ts_on) return pfail(b, RB_INVALID_REQUEST, kTsOff);
+  DeviceScope dev_scope(b->device);
+  std::vector<int32_t> w;
+  rb_status r = read_rows(b, b->ts.win, 2 * static_cast<size_t>(kTsWindow) * 4, w);
+  if (r != RB_OK) return r;
+  for (int k = 0; k < 2; ++k)
+    for (int i = 0; i < kTsWindow; ++i)
+      for (int h = 0; h < b->P; ++h)
+        for (int s = 0; s < b->S; ++s)
+          out[((static_cast<size_t>(k) * kTsWindow + i) * b->P + h) * b->S + s] = w[ts_win_index(k, i, h, b->Spad, s)];
+  return RB_OK;
+}
+
+rb_status rb_debug_time_sync_average(int32_t device, const int32_t* local_sums, const int32_t* remote_sums, int32_t* out,
+                                     int64_t n) {
+  if (n <= 0) return RB_OK;
+  if (!local_sums || !remote_sums || !out) return RB_INVALID_REQUEST;
+  if (device < 0) {
+    for (int64_t i = 0; i < n; ++i) out[i] = time_sync_average(local_sums[i], remote_sums[i]);
+    return RB_OK;
+  }
+  DeviceScope dev_scope(device);
+  const size_t bytes = static_cast<size_t>(n) * 4;
+  int32_t* d = nullptr;
+  if (hipMalloc(&d, 3 * bytes) != hipSuccess) return RB_DEVICE_ERROR;
+  bool ok = hipMemcpy(d, local_sums, bytes, hipMemcpyHostToDevice) == hipSuccess &&
+            hipMemcpy(d + n, remote_sums, bytes, hipMemcpyHostToDevice) == hipSuccess;
+  if (ok) {
+    hipLaunchKernelGGL(time_sync_average_kernel, dim3(static_cast<unsigned>((n + 255) / 256)), dim3(256), 0, nullptr, d,
+                       d + n, d + 2 * n, n);
+    ok = hipGetLastError() == hipSuccess && hipMemcpy(out, d + 2 * n, bytes, hipMemcpyDeviceToHost) == hipSuccess;
+  }
+  (void)hipFree(d);
+  return ok ? RB_OK : RB_DEVICE_ERROR;
 }
 
 rb_status rb_p2p_read_desync_events(rb_p2p* b, uint32_t* counts, int32_t* frames, int32_t* handles,

@@ -22,6 +22,10 @@ int32_t rb_plugin_abi() { return RB_PLUGIN_ABI; }
 
 int32_t rb_plugin_players() { return RB_PLUGIN_GAME::kPlayers; }
 
+// The plugin's P2P kernels know P2PParams::tick_log (time sync, time_sync.hpp); a plugin built
+// before it lacks this symbol and the engine refuses rb_p2p_time_sync_enable for its game.
+int32_t rb_plugin_tick_log() { return 1; }
+
 // A new GameOps for `players` (must be the game's kPlayers), owned by the caller
 // (deleted through its virtual destructor); NULL on a mismatch.
 rb::GameOps* rb_plugin_make_ops(int32_t players, int32_t abi) {

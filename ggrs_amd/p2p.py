@@ -320,6 +320,93 @@ class P2PSession(_StreamOrdered):
                                                         nx.ctypes.data_as(ctypes.c_void_p)))
         return st, nx
 
+    # -- time sync (time_sync.rs; p2p_session.rs:551, 745-776; protocol.rs:268-300, 697-708)
+    def enable_time_sync(self, fps: int = 60) -> None:
+        """SessionBuilder::with_fps (builder.rs:186-199; DEFAULT_FPS 60) and the batch's time
+        sync on: from now on every run_ticks call also updates frames_ahead, the
+        per-endpoint advantages and the WaitRecommendation events.  Before the first tick, once."""
+        self._check(self._lib.rb_p2p_time_sync_enable(self._h, int(fps)))
+
+    def receive_quality(self, handle: int, rtt_ms=None, frame_advantage=None) -> None:
+        """The peer behind remote `handle` answered a QualityReport (rtt_ms: round trip in
+        milliseconds) or sent one (frame_advantage, an i8 on the wire): int32 CUDA tensors [S],
+        None leaves the value as it is.  Between run_ticks calls."""
+        import torch
+        ptrs, keep = [], []
+        for x in (rtt_ms, frame_advantage):
+            if x is None:
+                ptrs.append(None)
+                continue
+            p, k = _dev_ptr(x)
+            assert k.dtype == torch.int32 and tuple(k.shape) == (self.num_sessions,)
+            ptrs.append(p)
+            keep.append(k)
+        cur = self._pre()
+        st = self._lib.rb_p2p_receive_quality(self._h, int(handle), ptrs[0], ptrs[1])
+        self._post(cur, tuple(keep))
+        self._check(st)
+
+    def _time_sync(self):
+        S, P = self.num_sessions, self.num_players
+        fa = np.empty(S, np.int32)
+        la, ra, rtt = (np.empty((P, S), np.int32) for _ in range(3))
+        p = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+        self._check(self._lib.rb_p2p_read_time_sync(self._h, p(fa), p(la), p(ra), p(rtt)))
+        return fa, la, ra, rtt
+
+    def frames_ahead(self):
+        """P2PSession::frames_ahead (p2p_session.rs:551) per session, int32 [S]."""
+        return self._time_sync()[0]
+
+    def read_time_sync(self):
+        """(frames_ahead [S], local_frame_advantage [P, S], remote_frame_advantage [P, S], rtt_ms [P, S])."""
+        return self._time_sync()
+
+    def network_stats(self, handle: int):
+        """The NetworkStats fields this path owns (protocol.rs:294-300) for remote `handle`, each
+        int32 [S]: ping (ms), local_frames_behind, remote_frames_behind.  send_queue_len and
+        kbps_sent are the network layer's."""
+        if not 0 <= int(handle) < self.num_players or (self.local_mask >> int(handle)) & 1:  # p2p_session.rs:469-484
+            raise InvalidRequest("Given player handle not referring to a remote player or spectator")
+        _, la, ra, rtt = self._time_sync()
+        return {"ping": rtt[handle], "local_frames_behind": la[handle], "remote_frames_behind": ra[handle]}
+
+    def wait_recommendations(self):
+        """(counts [S], frames [S, E], skip_frames [S, E]): GGRSEvent::WaitRecommendation per
+        session since enable_time_sync, the newest E = RB_P2P_WAIT_EVENTS_KEPT in order with the
+        current_frame they were raised at (frame NULL_FRAME: none)."""
+        E = L.RB_P2P_WAIT_EVENTS_KEPT
+        n = np.empty(self.num_sessions, np.uint32)
+        fr = np.empty((self.num_sessions, E), np.int32)
+        sk = np.empty((self.num_sessions, E), np.int32)
+        p = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+        self._check(self._lib.rb_p2p_read_wait_recommendations(self._h, p(n), p(fr), p(sk)))
+        return n, fr, sk
+
+    def export_time_sync(self, frames_ahead=None, local_adv=None) -> None:
+        """frames_ahead [S] and local_frame_advantage [P, S] (the QualityReport payload per
+        endpoint) into int32 CUDA tensors, stream ordered, no synchronisation."""
+        import torch
+        S, P = self.num_sessions, self.num_players
+        ptrs, keep = [], []
+        for x, shape in ((frames_ahead, (S,)), (local_adv, (P, S))):
+            if x is None:
+                ptrs.append(None)
+                continue
+            assert x.is_cuda and x.is_contiguous() and x.dtype == torch.int32 and tuple(x.shape) == shape
+            ptrs.append(ctypes.c_void_p(x.data_ptr()))
+            keep.append(x)
+        cur = self._pre()
+        st = self._lib.rb_p2p_export_time_sync(self._h, ptrs[0], ptrs[1])
+        self._post(cur, tuple(keep), outputs=True)
+        self._check(st)
+
+    def debug_time_sync_windows(self):
+        """The TimeSync windows, int32 [2 (local, remote), 30, P, S] (tests)."""
+        out = np.empty((2, 30, self.num_players, self.num_sessions), np.int32)
+        self._check(self._lib.rb_p2p_debug_read_time_sync_windows(self._h, out.ctypes.data_as(ctypes.c_void_p)))
+        return out
+
     def debug_corrupt(self, session: int, word: int, xor_mask: int) -> None:
         """Flip canonical state word `word` of the live state and every cell of `session`."""
         st = self._lib.rb_p2p_debug_corrupt(self._h, int(session), int(word), ctypes.c_uint32(xor_mask & 0xFFFFFFFF))

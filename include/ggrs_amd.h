@@ -261,7 +261,9 @@ rb_status rb_launch_clock_read(rb_batch* b, uint64_t* start_end, int32_t cap, in
  * peer-reported disconnects arrive through rb_p2p_receive_peer_connect_status
  * (RB_P2P_FLAG_PEER_STATUS, below).  Spectators are batches of their own
  * (rb_spectator_*, below), fed by rb_p2p_export_confirmed_inputs; registering
- * them on the host (PlayerType::Spectator) and time sync are out of scope.
+ * them on the host (PlayerType::Spectator) is out of scope.  Time sync
+ * (frames_ahead, WaitRecommendation, the NetworkStats this path owns) is
+ * rb_p2p_time_sync_enable, below.
  * ======================================================================== */
 typedef struct rb_p2p rb_p2p;
 
@@ -515,6 +517,78 @@ rb_status rb_p2p_export_confirmed_inputs(rb_p2p* b, void* inputs_by_frame, int32
  * (both as the last export left them; before the first: OK and 0).  Either
  * pointer may be NULL.  Synchronises. */
 rb_status rb_p2p_read_export_status(rb_p2p* b, int32_t* status, int32_t* next_frame);
+
+/* ---- Time sync (time_sync.rs; protocol.rs:268-277, 439-455, 697-708;
+ * p2p_session.rs:745-776).  Every endpoint keeps two 30-frame windows of its
+ * local and remote frame advantage; a session's frames_ahead is the maximum
+ * over its connected remote players of the windows' halved average difference,
+ * and every 60 frames at most a session that runs 3 or more frames ahead
+ * raises GGRSEvent::WaitRecommendation{skip_frames} (lib.rs:151-155).  Time
+ * sync never feeds back into a session inside a call: it runs as a launch of
+ * its own after the ticks of every rb_p2p_run_ticks call, on the batch's
+ * stream, from a per-tick log those ticks write, and
+ * the caller acts on its results between calls.
+ *
+ * rb_p2p_time_sync_enable is SessionBuilder::with_fps (builder.rs:186-199):
+ * fps <= 0 is RB_INVALID_REQUEST "FPS should be higher than 0."; so is a second
+ * call, or a call after the batch's first tick.  rb_p2p_config is unchanged.
+ * Works with every configuration of rb_p2p_run_ticks (sparse saving, desync
+ * detection, peers' connect status, both fan-out forms);
+ * rb_p2p_run_ticks_packets with time sync on is RB_INVALID_REQUEST (there the
+ * newest received frame is decided inside the kernel).  Per tick, with cur =
+ * current_frame at the tick's entry: every remote handle h still connected at
+ * the tick's entry takes last_recv = min(remote_upto[t][h][s], remote_frames - 1)
+ * and, unless that is RB_NULL_FRAME, local_frame_advantage[h] = last_recv +
+ * ((rtt_ms[h] / 2) * fps) / 1000 - cur (i32, truncating); frames_ahead and the
+ * event follow; a tick that gets past add_local_input (no
+ * PredictionThreshold) writes both windows at slot (cur + input_delay) % 30 for
+ * every remote handle connected after update_player_disconnects.  A session
+ * that panics stops its time sync at that tick.
+ * The tick log grows to the largest n_ticks a call has passed: a call with more
+ * ticks than any before it (the first included) synchronises the batch's
+ * stream and allocates inside rb_p2p_run_ticks.  A caller that captures its
+ * launches into a graph makes one uncaptured call of its largest n_ticks first. */
+#define RB_P2P_WAIT_EVENTS_KEPT 8 /* newest WaitRecommendation events kept per session */
+rb_status rb_p2p_time_sync_enable(rb_p2p* b, int32_t fps);
+
+/* UdpProtocol::on_quality_reply / on_quality_report (protocol.rs:697-708) for
+ * the endpoint of remote handle `handle` in every session: round_trip_time in
+ * milliseconds and the peer's frame advantage, device int32 [S] each; either
+ * may be NULL, which leaves that value as it is.  Stream ordered, called between
+ * rb_p2p_run_ticks calls.  frame_advantage is an i8 on the wire: the caller
+ * keeps it in -128..127; rtt_ms must keep (rtt_ms / 2) * fps inside int32.
+ * RB_INVALID_REQUEST: a local handle, or time sync off. */
+rb_status rb_p2p_receive_quality(rb_p2p* b, int32_t handle, const int32_t* rtt_ms, const int32_t* frame_advantage);
+
+/* frames_ahead (p2p_session.rs:551) into frames_ahead_dev int32 [S] and every
+ * endpoint's local_frame_advantage, the payload of the QualityReport the batch
+ * owes its peer (protocol.rs:516-524), into local_adv_dev int32 [num_players][S]
+ * (0 for local handles): device memory, stream ordered, no synchronisation.
+ * Either pointer may be NULL. */
+rb_status rb_p2p_export_time_sync(rb_p2p* b, int32_t* frames_ahead_dev, int32_t* local_adv_dev);
+
+/* The same to host arrays, with the rest of NetworkStats this path owns
+ * (protocol.rs:294-300): frames_ahead [S]; local_adv (local_frames_behind),
+ * remote_adv (remote_frames_behind) and rtt_ms (ping), each [num_players][S].
+ * send_queue_len and kbps_sent are the network layer's.  Any pointer may be
+ * NULL.  Synchronises. */
+rb_status rb_p2p_read_time_sync(rb_p2p* b, int32_t* frames_ahead, int32_t* local_adv, int32_t* remote_adv,
+                                int32_t* rtt_ms);
+
+/* WaitRecommendation events per session: counts[S] since enable, and the newest
+ * RB_P2P_WAIT_EVENTS_KEPT in order as current_frame / skip_frames, each
+ * [S][RB_P2P_WAIT_EVENTS_KEPT] (frame RB_NULL_FRAME, skip_frames 0: none).  Any
+ * pointer may be NULL.  Synchronises. */
+rb_status rb_p2p_read_wait_recommendations(rb_p2p* b, uint32_t* counts, int32_t* frames, int32_t* skip_frames);
+
+/* For tests: the windows, out[2 local, remote][30][num_players][S].  Synchronises. */
+rb_status rb_p2p_debug_read_time_sync_windows(rb_p2p* b, int32_t* out);
+
+/* TimeSync::average_frame_advantage (time_sync.rs:30-39) from the windows' sums
+ * for n host (local_sum, remote_sum) pairs: device < 0 on the host, else by a
+ * kernel on that device (the same function, time_sync.hpp). */
+rb_status rb_debug_time_sync_average(int32_t device, const int32_t* local_sums, const int32_t* remote_sums,
+                                     int32_t* out, int64_t n);
 
 /* Fault injection for tests (ex_game.rs:211-215 trigger_desync, generalised):
  * XOR `xor_mask` into canonical state word `word` of `session`'s live state

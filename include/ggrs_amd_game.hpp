@@ -57,7 +57,12 @@
 /* ABI of the plugin entry points (rb_plugin_abi); bump when the engine's
  * kernel parameter structs or the layout of the state they point to change
  * (7: the packed P2P bookkeeping rows; 8: the spectator launcher, a new
- * last virtual of the game's launcher table). */
+ * last virtual of the game's launcher table).  The time-sync tick log
+ * needed no bump: its pointer shares a word of the P2P launch parameters
+ * with a field only packet-fed launches use, so the layout is unchanged and
+ * a plug-in built before it runs as before.  Such a plug-in cannot log
+ * ticks: the engine asks for rb_plugin_tick_log (plugin.hip) and refuses
+ * rb_p2p_time_sync_enable for a plug-in without it. */
 #define RB_PLUGIN_ABI 8
 
 #endif /* GGRS_AMD_GAME_HPP */

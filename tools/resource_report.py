@@ -2,6 +2,15 @@
 -Rpass-analysis=kernel-resource-usage, on the Makefile's flags), one line per kernel.
 
     python3 tools/resource_report.py > profiles/spectator_resource_usage.txt
+
+With --against REPORT (a report of another commit, made the same way) every p2p_kernel line is
+followed by how it compares: the instantiation of the same name there, where a trailing
+", false" template argument this commit added (a flag that is off) is dropped from the name.
+
+    python3 tools/resource_report.py --against parent_report.txt ops_exgame_p2.hip ...
+
+profiles/time_sync_resource_usage.txt was made that way against
+profiles/time_sync_resource_usage_parent.txt, this tool's report of the commit before it.
 """
 import os
 import re
@@ -13,10 +22,29 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "ggrs_amd", "csrc")
 FLAGS = ["-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-ffp-contract=off",
          "-fhip-fp32-correctly-rounded-divide-sqrt", "-DRB_EXPERIMENTS=0"]
+AGAINST = None
+if "--against" in sys.argv:
+    i = sys.argv.index("--against")
+    AGAINST = sys.argv[i + 1]
+    del sys.argv[i:i + 2]
 TUS = sys.argv[1:] or ["ops_exgame_p2.hip", "ops_exgame_p3.hip", "ops_exgame_p4.hip", "ops_brawler_p2.hip", "ops_stub.hip"]
 
 
+def load_report(path):
+    """{(translation unit, kernel): the eight numbers} of a report this tool wrote."""
+    out, tu = {}, None
+    for line in open(path):
+        if line.startswith("## "):
+            tu = line[3:].strip()
+        elif line.strip() and not line.startswith("#"):
+            f = line.split(None, 8)
+            out[tu, f[8].strip()] = tuple(int(x) for x in f[:8])
+    return out
+
+
 def main():
+    base = load_report(AGAINST) if AGAINST else None
+    same = changed = added = 0
     print(f"# {' '.join(FLAGS)} (+ -mllvm -amdgpu-sched-strategy=max-ilp for ops_exgame_p*, as the Makefile)")
     print(f"# {'VGPR':>4s} {'AGPR':>4s} {'SGPR':>4s} {'SGPR spill':>10s} {'VGPR spill':>10s} {'scratch B/lane':>14s} "
           f"{'waves/SIMD':>10s} {'LDS B':>6s}  kernel")
@@ -44,10 +72,27 @@ def main():
             n = subprocess.run(["c++filt", r["name"]], capture_output=True, text=True).stdout.strip()
             if "kernel" not in n:
                 continue
-            n = n.replace("void rb::", "").replace("rb::", "")
+            n = n.replace("(anonymous namespace)::", "")
+            n = n[5:] if n.startswith("void ") else n
+            n = n.replace("rb::", "")
             n = n.split("(")[0]
-            print(f"  {r.get('v', 0):4d} {r.get('a', 0):4d} {r.get('s', 0):4d} {r.get('ss', 0):10d} {r.get('vs', 0):10d} "
-                  f"{r.get('sc', 0):14d} {r.get('o', 0):10d} {r.get('l', 0):6d}  {n}")
+            vals = tuple(r.get(k, 0) for k in ("v", "a", "s", "ss", "vs", "sc", "o", "l"))
+            note = ""
+            if base is not None and n.startswith("p2p_kernel<"):
+                old = base.get((tu, n)) or (base.get((tu, n[:-len(", false>")] + ">")) if n.endswith(", false>") else None)
+                if old is None:
+                    added += 1
+                    note = "   [new]"
+                elif old == vals:
+                    same += 1
+                    note = "   [= parent]"
+                else:
+                    changed += 1
+                    note = f"   [CHANGED, parent: {' '.join(map(str, old))}]"
+            print(f"  {vals[0]:4d} {vals[1]:4d} {vals[2]:4d} {vals[3]:10d} {vals[4]:10d} "
+                  f"{vals[5]:14d} {vals[6]:10d} {vals[7]:6d}  {n}{note}")
+    if base is not None:
+        print(f"# p2p_kernel instantiations against {os.path.basename(AGAINST)}: {same} unchanged, {changed} changed, {added} new")
 
 
 if __name__ == "__main__":
