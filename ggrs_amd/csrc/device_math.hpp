@@ -33,6 +33,16 @@ struct SinCos {
 
 __device__ __forceinline__ uint32_t abstop12(float x) { return (__float_as_uint(x) >> 20) & 0x7ff; }
 
+// Three-input bit operations as one v_bitop3_b32 each (the truth table is the
+// immediate: bit (a << 2 | b << 1 | c) of it is the result for input bits a, b, c).
+// bit_select: m ? a : b per bit.  xor_and: a ^ (b & c).
+__device__ __forceinline__ uint32_t bit_select(uint32_t m, uint32_t a, uint32_t b) {
+  return static_cast<uint32_t>(__builtin_amdgcn_bitop3_b32(m, a, b, 0xCA));
+}
+__device__ __forceinline__ uint32_t xor_and(uint32_t a, uint32_t b, uint32_t c) {
+  return static_cast<uint32_t>(__builtin_amdgcn_bitop3_b32(a, b, c, 0x78));
+}
+
 // sincosf.h sinf_poly(x, x2, p, n) for n even (sine polynomial); s1..s3 are the
 // same in both __sincosf_table rows.
 __device__ __forceinline__ double sin_poly(double x, double x2) {
@@ -83,18 +93,22 @@ __device__ __forceinline__ SinCos sincosf_glibc(float y, uint32_t* unexpected) {
   double xr = __builtin_fma(-static_cast<double>(n), hpi, x);
   const double x2 = xr * xr;
   // sign[4] = {1,-1,-1,1}: negate when (n & 3) is 1 or 2, i.e. bit 1 of n + 1.
-  // Adding 2^31 to the high word flips the sign bit (no carry out of bit 31).
-  const uint32_t sflip = (static_cast<uint32_t>(n + 1) >> 1) & 1u;
-  xr = __hiloint2double(static_cast<int>(static_cast<uint32_t>(__double2hiint(xr)) + (sflip << 31)), __double2loint(xr));
+  // Bit 1 moved to bit 31 and XORed onto the high word flips the sign: one
+  // shift and one three-input bit operation (a ^ (b & c)) per flip.
+  const uint32_t sflip = static_cast<uint32_t>(n + 1) << 30;
+  xr = __hiloint2double(static_cast<int>(xor_and(static_cast<uint32_t>(__double2hiint(xr)), sflip, 0x80000000u)),
+                        __double2loint(xr));
   const float sp = static_cast<float>(sin_poly(xr, x2));
   // __sincosf_table[1] (n & 2) negates every cosine coefficient: negate the
   // rounded result (rounding is sign-symmetric).
-  const uint32_t cflip = (static_cast<uint32_t>(n) >> 1) & 1u;
-  const float cp = __uint_as_float(__float_as_uint(static_cast<float>(cos_poly(x2))) + (cflip << 31));
+  const uint32_t cflip = static_cast<uint32_t>(n) << 30;
+  const float cp = __uint_as_float(xor_and(__float_as_uint(static_cast<float>(cos_poly(x2))), cflip, 0x80000000u));
   SinCos r;
-  // sinf: n even -> sine poly, odd -> cosine poly; cosf uses n ^ 1.
-  r.s = (n & 1) ? cp : sp;
-  r.c = (n & 1) ? sp : cp;
+  // sinf: n even -> sine poly, odd -> cosine poly; cosf uses n ^ 1.  Bit 0 of n
+  // spread to a mask (one v_bfe_i32) and two bit selects: no compare, no VCC.
+  const uint32_t odd = 0u - (static_cast<uint32_t>(n) & 1u);
+  r.s = __uint_as_float(bit_select(odd, __float_as_uint(cp), __float_as_uint(sp)));
+  r.c = __uint_as_float(bit_select(odd, __float_as_uint(sp), __float_as_uint(cp)));
   // |y| < 2^-12: glibc returns (y, 1).  Inline: ex_game's rotations sit at
   // exactly 0 for long stretches (State::new gives player 1 rot = 0).
   if constexpr (!kInRange) {

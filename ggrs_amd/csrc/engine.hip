@@ -93,6 +93,32 @@ __global__ void inrange_kernel(uint32_t first, int64_t n, float* __restrict__ ou
   out[5 * n + i] = rem_euclid<true>(x - E::kRotationSpeed, 2.0f * E::kPi);
 }
 
+// ExGame::clamp_position (one median of three) against the reference's two steps x.max(0).min(L)
+// (ex_game.rs:311-314) for the floats with bits first + i and both limits (rb_debug_exgame_position_clamp).
+// diff[0] counts the patterns whose two forms differ in any bit for either limit, diff[1] is the
+// smallest such pattern; signalling NaNs are left out (a position is the result of an f32 add,
+// which never yields one).  out, when given, receives the one-instruction form: [2][n], L = 600, 800.
+__global__ void position_clamp_kernel(uint32_t first, int64_t n, unsigned long long* __restrict__ diff,
+                                      float* __restrict__ out) {
+  const int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  using E = ExGame<2, true>;
+  const uint32_t bits = first + static_cast<uint32_t>(i);
+  const float x = __uint_as_float(bits);
+  const float a0 = E::clamp_position(x, E::kWidth), a1 = E::clamp_position(x, E::kHeight);
+  const float b0 = fminf(fmaxf(x, 0.0f), E::kWidth), b1 = fminf(fmaxf(x, 0.0f), E::kHeight);
+  if (out) {
+    out[i] = a0;
+    out[n + i] = a1;
+  }
+  const uint32_t mag = bits & 0x7fffffffu;
+  const bool snan = mag > 0x7f800000u && mag < 0x7fc00000u;
+  if (!snan && (__float_as_uint(a0) != __float_as_uint(b0) || __float_as_uint(a1) != __float_as_uint(b1))) {
+    atomicAdd(&diff[0], 1ull);
+    atomicMin(&diff[1], static_cast<unsigned long long>(bits));
+  }
+}
+
 __global__ void clamp_kernel(const float* __restrict__ vx, const float* __restrict__ vy, float* __restrict__ ox,
                              float* __restrict__ oy, int64_t n) {
   const int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
@@ -962,6 +988,27 @@ rb_status rb_debug_exgame_inrange(int32_t device, uint32_t first_bits, int64_t n
                      dev_out);
   if (hipGetLastError() != hipSuccess) return RB_DEVICE_ERROR;
   return hipDeviceSynchronize() == hipSuccess ? RB_OK : RB_DEVICE_ERROR;
+}
+
+rb_status rb_debug_exgame_position_clamp(int32_t device, uint32_t first_bits, int64_t n, uint64_t* diff, float* dev_out) {
+  if (n <= 0 || !diff || static_cast<uint64_t>(first_bits) + static_cast<uint64_t>(n) > (1ull << 32)) return RB_INVALID_REQUEST;
+  if (hipSetDevice(device) != hipSuccess) return RB_DEVICE_ERROR;
+  unsigned long long* d = nullptr;
+  const unsigned long long init[2] = {0ull, ~0ull};
+  hipError_t e = hipMalloc(&d, sizeof(init));
+  if (e == hipSuccess) e = hipMemcpy(d, init, sizeof(init), hipMemcpyHostToDevice);
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(position_clamp_kernel, dim3(static_cast<unsigned>((n + 255) / 256)), dim3(256), 0, nullptr, first_bits,
+                       n, d, dev_out);
+    e = hipGetLastError();
+  }
+  unsigned long long h[2] = {0, 0};
+  if (e == hipSuccess) e = hipMemcpy(h, d, sizeof(h), hipMemcpyDeviceToHost);
+  if (d) (void)hipFree(d);
+  if (e != hipSuccess) return fail(nullptr, RB_DEVICE_ERROR, std::string("rb_debug_exgame_position_clamp: ") + hipGetErrorString(e));
+  diff[0] = h[0];
+  diff[1] = h[1];
+  return RB_OK;
 }
 
 rb_status rb_debug_speed_clamp(int32_t device, const float* vx, const float* vy, float* ox, float* oy, int64_t n) {

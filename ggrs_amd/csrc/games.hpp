@@ -154,6 +154,14 @@ struct ExGame {
   }
 
   // ex_game.rs:300-304: if |v| > MAX_SPEED { v = v * MAX_SPEED / |v| }.
+  // kWave (the fused steady ticks): the choice between the short division
+  // sequence and the full IEEE division is made once for the wave instead of
+  // per lane.  The full division is correctly rounded for every operand, and
+  // the short sequence equals it on its range, so when any clamping lane's
+  // operands are outside that range all clamping lanes take the full form's
+  // results, else all keep the short one's: the same bits either way, one
+  // scalar branch over a cold block and no exec mask nested inside the clamp's.
+  template <bool kWave = false>
   __device__ static void speed_clamp(float& vx, float& vy) {
     // mag > 7 <=> vx^2+vy^2 > 49: sqrt is correctly rounded and monotone,
     // sqrt(49) = 7 exactly, and the next float above 49 (49 + 2^-18) has a
@@ -164,7 +172,17 @@ struct ExGame {
     if (m2 > kMaxSpeed * kMaxSpeed) {
       const float mag = sqrt_rn_above_one(m2);
       const float nx = vx * kMaxSpeed, ny = vy * kMaxSpeed;
-      if (mag < 256.0f && __builtin_fabsf(nx) >= 0x1p-96f && __builtin_fabsf(ny) >= 0x1p-96f) {
+      if constexpr (kWave) {
+        // both components at once: neither nx nor ny is a NaN here (m2 would be one, and not > 49)
+        const bool ok = mag < 256.0f && fminf(__builtin_fabsf(nx), __builtin_fabsf(ny)) >= 0x1p-96f;
+        const float r = rcp_refined(mag);
+        vx = div_rn_unscaled(nx, mag, r);
+        vy = div_rn_unscaled(ny, mag, r);
+        if (__builtin_expect(__any(!ok), 0)) {  // (replaces the short sequence's results on every clamping lane)
+          vx = nx / mag;
+          vy = ny / mag;
+        }
+      } else if (mag < 256.0f && __builtin_fabsf(nx) >= 0x1p-96f && __builtin_fabsf(ny) >= 0x1p-96f) {
         const float r = rcp_refined(mag);  // both divisions share the denominator
         vx = div_rn_unscaled(nx, mag, r);
         vy = div_rn_unscaled(ny, mag, r);
@@ -173,6 +191,16 @@ struct ExGame {
         vy = ny / mag;
       }
     }
+  }
+  // x.max(0.0).min(limit) (ex_game.rs:311-314) as one v_med3_f32.  x is the sum
+  // of an f32 add, so never a signalling NaN; for a quiet NaN the median
+  // returns the minimum of the other two, 0, as the two-step form does, and
+  // -0 orders below +0 in both (rb_debug_exgame_position_clamp sweeps every
+  // bit pattern of both forms on the device).
+  __device__ static float clamp_position(float x, float limit) { return __builtin_amdgcn_fmed3f(x, 0.0f, limit); }
+  // thrust ? t : -0.0 from the all-ones / all-zeros thrust mask
+  __device__ static float thrust_or_neg_zero(uint32_t thm, float t) {
+    return __uint_as_float(bit_select(thm, __float_as_uint(t), 0x80000000u));
   }
 
   // State::advance (ex_game.rs:259-321) for one player.  Compiled with
@@ -238,6 +266,9 @@ struct ExGame {
   struct Prep {
     float tx[kPlayersPerLane][N], ty[kPlayersPerLane][N];  // thrust added in frame k (-0 when none)
     float rot[kPlayersPerLane][N + 1];                       // rotation before frame k (rot[N]: after the last)
+    // The position limits in VGPRs, set once per tick: v_med3_f32 takes no literal, and as two more
+    // scalar constants they cost the kernel an SGPR spill slot.
+    float xlim, ylim;
   };
   // One frame's input as this lane's players act on it (decoded once, when the
   // input enters the steady kernel's window): the signed thrust speed, the
@@ -245,7 +276,11 @@ struct ExGame {
   // RIGHT" (bit selects, no compare per use).
   struct Dec {
     float sp[kPlayersPerLane], rd[kPlayersPerLane];
-    uint32_t thm[kPlayersPerLane], rom[kPlayersPerLane];
+    // the two masks as one 64-bit value (thrust low, rotation high): the window of decoded frames
+    // slides by one 64-bit move per pair instead of two 32-bit ones, and reading a half is free
+    uint64_t masks[kPlayersPerLane];
+    __device__ uint32_t thm(int j) const { return static_cast<uint32_t>(masks[j]); }
+    __device__ uint32_t rom(int j) const { return static_cast<uint32_t>(masks[j] >> 32); }
   };
   __device__ static Dec decode(InRec rec, int lane) {
     Dec d;
@@ -263,15 +298,19 @@ struct ExGame {
       uint32_t rd = __float_as_uint(kRotationSpeed) | (((input >> 2) & 1u) << 31);   // left ? -R : R
       uint32_t thm = 0u - (x & 1u), rom = 0u - ((x >> 2) & 1u);
       asm volatile("" : "+v"(sp), "+v"(rd), "+v"(thm), "+v"(rom));
+      uint64_t masks = static_cast<uint64_t>(thm) | (static_cast<uint64_t>(rom) << 32);
+      asm volatile("" : "+v"(masks));
       d.sp[j] = __uint_as_float(sp);
       d.rd[j] = __uint_as_float(rd);
-      d.thm[j] = thm;
-      d.rom[j] = rom;
+      d.masks[j] = masks;
     }
     return d;
   }
   template <bool kInRange, int N>
   __device__ static void prepare(const uint32_t (&w)[NWL], const Dec (&dec)[N], Prep<N>& pr, uint32_t* unexpected) {
+    pr.xlim = kWidth;
+    pr.ylim = kHeight;
+    asm("" : "+v"(pr.xlim), "+v"(pr.ylim));
 #pragma unroll
     for (int j = 0; j < kPlayersPerLane; ++j) {
       float rot = __uint_as_float(w[5 * j + 4]);
@@ -281,11 +320,10 @@ struct ExGame {
         pr.rot[j][k] = rot;
         const SinCos sc = sincosf_glibc<kInRange>(rot, unexpected);
         const float tx = d.sp[j] * sc.c, ty = d.sp[j] * sc.s;
-        // thrust ? t : -0.0 as a bit select on the mask
-        pr.tx[j][k] = __uint_as_float((d.thm[j] & __float_as_uint(tx)) | (~d.thm[j] & 0x80000000u));
-        pr.ty[j][k] = __uint_as_float((d.thm[j] & __float_as_uint(ty)) | (~d.thm[j] & 0x80000000u));
+        pr.tx[j][k] = thrust_or_neg_zero(d.thm(j), tx);
+        pr.ty[j][k] = thrust_or_neg_zero(d.thm(j), ty);
         const float r1 = rem_euclid_near<kInRange>(rot + d.rd[j], 2.0f * kPi);
-        rot = __uint_as_float((d.rom[j] & __float_as_uint(r1)) | (~d.rom[j] & __float_as_uint(rot)));
+        rot = __uint_as_float(bit_select(d.rom(j), __float_as_uint(r1), __float_as_uint(rot)));
       }
       pr.rot[j][N] = rot;
     }
@@ -299,10 +337,8 @@ struct ExGame {
       const float old_x = __uint_as_float(p[0]), old_y = __uint_as_float(p[1]);
       float vx = __uint_as_float(p[2]) * kFriction + pr.tx[j][k];
       float vy = __uint_as_float(p[3]) * kFriction + pr.ty[j][k];
-      speed_clamp(vx, vy);
-      float x = old_x + vx, y = old_y + vy;
-      x = fminf(fmaxf(x, 0.0f), kWidth);
-      y = fminf(fmaxf(y, 0.0f), kHeight);
+      speed_clamp<true>(vx, vy);
+      const float x = clamp_position(old_x + vx, pr.xlim), y = clamp_position(old_y + vy, pr.ylim);
       p[0] = __float_as_uint(x);
       p[1] = __float_as_uint(y);
       p[2] = __float_as_uint(vx);
@@ -337,9 +373,7 @@ struct ExGame {
       special |= (clamp && !ok) ? 1u : 0u;
       vx = clamp ? qx : vx;
       vy = clamp ? qy : vy;
-      float x = old_x + vx, y = old_y + vy;
-      x = fminf(fmaxf(x, 0.0f), kWidth);
-      y = fminf(fmaxf(y, 0.0f), kHeight);
+      const float x = clamp_position(old_x + vx, kWidth), y = clamp_position(old_y + vy, kHeight);
       p[0] = __float_as_uint(x);
       p[1] = __float_as_uint(y);
       p[2] = __float_as_uint(vx);
@@ -367,8 +401,7 @@ struct ExGame {
       const float sp = up ? kMovementSpeed : -kMovementSpeed;
       const float tx = sp * sc.c, ty = sp * sc.s;  // -(S * c) == (-S) * c
       const uint32_t thm = up != down ? ~0u : 0u;
-      const float txm = __uint_as_float((thm & __float_as_uint(tx)) | (~thm & 0x80000000u));
-      const float tym = __uint_as_float((thm & __float_as_uint(ty)) | (~thm & 0x80000000u));
+      const float txm = thrust_or_neg_zero(thm, tx), tym = thrust_or_neg_zero(thm, ty);
       const float r1 = rem_euclid_near<true>(rot + (left ? -kRotationSpeed : kRotationSpeed), 2.0f * kPi);
       float vx = __uint_as_float(p[2]) * kFriction + txm;
       float vy = __uint_as_float(p[3]) * kFriction + tym;
@@ -382,9 +415,8 @@ struct ExGame {
       special |= (clamp && !ok) ? 1u : 0u;
       vx = clamp ? qx : vx;
       vy = clamp ? qy : vy;
-      float x = __uint_as_float(p[0]) + vx, y = __uint_as_float(p[1]) + vy;
-      x = fminf(fmaxf(x, 0.0f), kWidth);
-      y = fminf(fmaxf(y, 0.0f), kHeight);
+      const float x = clamp_position(__uint_as_float(p[0]) + vx, kWidth);
+      const float y = clamp_position(__uint_as_float(p[1]) + vy, kHeight);
       p[0] = __float_as_uint(x);
       p[1] = __float_as_uint(y);
       p[2] = __float_as_uint(vx);

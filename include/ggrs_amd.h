@@ -219,6 +219,15 @@ rb_status rb_debug_sincosf(int32_t device, const float* x, float* sin_out, float
  * [6][n] (sin, cos, step up, step down, step up, step down).  Synchronises. */
 rb_status rb_debug_exgame_inrange(int32_t device, uint32_t first_bits, int64_t n, float* dev_out);
 
+/* ex_game's position clamp x.max(0).min(L) (ex_game.rs:311-314) as the fused steady ticks run it,
+ * one median of three, against the two-step form, both evaluated on the device for the n floats
+ * whose bits are first_bits, first_bits + 1, ... (first_bits + n <= 2^32) and for both limits
+ * (600 and 800).  diff[0] (host) = the number of patterns whose two forms differ in any bit,
+ * diff[1] = the smallest such pattern (all ones when none); signalling NaNs (0x7F800001-0x7FBFFFFF,
+ * 0xFF800001-0xFFBFFFFF) are left out: a position is the result of an f32 add.  dev_out: null, or
+ * device memory [2][n] for the one-instruction form's results (L = 600, L = 800).  Synchronises. */
+rb_status rb_debug_exgame_position_clamp(int32_t device, uint32_t first_bits, int64_t n, uint64_t* diff, float* dev_out);
+
 /* Device evaluation of ex_game's speed clamp (ex_game.rs:300-304: v * MAX_SPEED
  * / |v| when |v| > MAX_SPEED) for n host (vx, vy) pairs — pins the short exact
  * sqrt/division sequences of device_math.hpp against host IEEE arithmetic. */
