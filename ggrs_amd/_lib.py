@@ -178,6 +178,9 @@ SIGNATURES = [
     ("rb_p2p_read_time_sync", _I32, [_P, _P, _P, _P, _P]),
     ("rb_p2p_read_wait_recommendations", _I32, [_P, _P, _P, _P]),
     ("rb_p2p_debug_read_time_sync_windows", _I32, [_P, _P]),
+    ("rb_p2p_run_ticks_paced", _I32, [_P, _I32, _P, ctypes.c_int64, _P, _P, _I32, _P]),
+    ("rb_p2p_pace", _I32, [_P, _P]),
+    ("rb_p2p_read_pacing", _I32, [_P, _P]),
     ("rb_debug_time_sync_average", _I32, [_I32, _P, _P, _P, ctypes.c_int64]),
     ("rb_p2p_profile_enable", _I32, [_P, _I32]),
     ("rb_p2p_profile_take", _I32, [_P, ctypes.POINTER(ctypes.c_double), _PI32]),

@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "kernels.hpp"
+#include "pacing.hpp"
 #include "time_sync.hpp"
 
 using namespace rb;
@@ -45,6 +46,7 @@ struct rb_p2p {
   bool ts_on = false;
   int32_t* ts_log = nullptr;          // [ts_log_ticks][kTlRows][Spad] the tick log, every kTlEnd row unwritten between calls
   int32_t ts_log_ticks = 0;
+  PaceParams pace{};                  // rb_p2p_run_ticks_paced / rb_p2p_pace: the status view, parked ticks, the pacer's accumulator
   bool ticked = false;                // a tick has run (rb_p2p_time_sync_enable comes before the first)
   bool prof = false;
   std::vector<std::pair<hipEvent_t, hipEvent_t>> prof_ev;
@@ -106,6 +108,9 @@ void free_all(rb_p2p* b) {
   if (b->ts.state) (void)hipFree(b->ts.state);
   if (b->ts.win) (void)hipFree(b->ts.win);
   if (b->ts_log) (void)hipFree(b->ts_log);
+  if (b->pace.view) (void)hipFree(b->pace.view);
+  if (b->pace.parked) (void)hipFree(b->pace.parked);
+  if (b->pace.acc) (void)hipFree(b->pace.acc);
   for (auto& pr : b->prof_ev) {
     (void)hipEventDestroy(pr.first);
     (void)hipEventDestroy(pr.second);
@@ -278,6 +283,26 @@ void image_from_planes(const rb_p2p* b, const std::vector<uint32_t>& planes, int
   b->ops->image(w.data(), frame, out);
 }
 }  // namespace
+
+namespace {
+// The pacing buffers, made by the first call that needs them: nothing parked yet, acc = 0.
+rb_status pace_reserve(rb_p2p* b) {
+  if (b->pace.view) return RB_OK;
+  const size_t bytes = static_cast<size_t>(b->Spad) * 4;
+  P2P_TRY(b, hipMalloc(&b->pace.view, bytes));
+  P2P_TRY(b, hipMalloc(&b->pace.parked, bytes));
+  P2P_TRY(b, hipMalloc(&b->pace.acc, bytes));
+  P2P_TRY(b, hipMemsetAsync(b->pace.view, 0, bytes, b->stream));
+  P2P_TRY(b, hipMemsetAsync(b->pace.parked, 0, bytes, b->stream));
+  P2P_TRY(b, hipMemsetAsync(b->pace.acc, 0, bytes, b->stream));
+  return RB_OK;
+}
+template <int IB>
+auto poll_kernel_of(int P) {
+  return P == 1 ? p2p_poll_kernel<IB, 1> : P == 2 ? p2p_poll_kernel<IB, 2> : P == 3 ? p2p_poll_kernel<IB, 3> : p2p_poll_kernel<IB, 4>;
+}
+}  // namespace
+
 
 extern "C" {
 
@@ -640,11 +665,11 @@ rb_status ts_log_reserve(rb_p2p* b, int32_t n) {
   return RB_OK;
 }
 // p2p_time_sync_kernel over the n ticks the P2P launch(es) of this call just logged
-rb_status ts_launch(rb_p2p* b, const P2PParams& p, int32_t n) {
+rb_status ts_launch(rb_p2p* b, const P2PParams& p, int32_t n, const int32_t* status = nullptr) {
   const dim3 grid((b->Spad + 255) / 256), block(256);  // lanes past S do nothing
   auto k = b->P == 1 ? p2p_time_sync_kernel<1> : b->P == 2 ? p2p_time_sync_kernel<2>
          : b->P == 3 ? p2p_time_sync_kernel<3> : p2p_time_sync_kernel<4>;
-  hipLaunchKernelGGL(k, grid, block, 0, b->stream, b->ts, b->ts_log, static_cast<int64_t>(kTlRows) * b->Spad, p.upto, p.upto_stride, b->status, n,
+  hipLaunchKernelGGL(k, grid, block, 0, b->stream, b->ts, b->ts_log, static_cast<int64_t>(kTlRows) * b->Spad, p.upto, p.upto_stride, status ? status : b->status, n,
                      b->S, b->Spad, p.remote_frames, b->cfg.local_mask, b->cfg.input_delay, b->peer.on);
   P2P_TRY(b, hipGetLastError());
   return RB_OK;
@@ -745,6 +770,105 @@ rb_status rb_p2p_run_ticks(rb_p2p* b, int32_t n_ticks, const void* local_inputs,
     if (r != RB_OK) return r;
   }
   if (b->fanout) return fan_after(b, n_ticks);
+  return RB_OK;
+}
+
+rb_status rb_p2p_run_ticks_paced(rb_p2p* b, int32_t n_ticks, const void* local_inputs, int64_t local_stride,
+                                 const int32_t* remote_upto, const void* remote_inputs, int32_t remote_frames,
+                                 const uint8_t* run_mask) {
+  if (!run_mask) return rb_p2p_run_ticks(b, n_ticks, local_inputs, local_stride, remote_upto, remote_inputs, remote_frames);
+  if (n_ticks <= 0) return RB_OK;
+  if (!local_inputs || !remote_upto || !remote_inputs || remote_frames <= 0)
+    return pfail(b, RB_INVALID_REQUEST, "rb_p2p_run_ticks_paced: missing input tensor");
+  if (b->fanout)  // the move-to-front rows and branch validity under a parked poll: a later step
+    return pfail(b, RB_INVALID_REQUEST, "rb_p2p_run_ticks_paced: a batch with the fan-out takes rb_p2p_run_ticks");
+  const int IB = b->ops->input_bytes;
+  if (IB != 1 && IB != 4) return pfail(b, RB_INVALID_REQUEST, "rb_p2p_run_ticks_paced: inputs of 1 or 4 bytes");
+  P2PParams p = base_params(b);
+  p.local_in = static_cast<const uint8_t*>(local_inputs);
+  p.local_stride = local_stride;
+  p.upto = remote_upto;
+  p.upto_stride = static_cast<int64_t>(b->P) * b->S;
+  p.remote_in = static_cast<const uint8_t*>(remote_inputs);
+  p.remote_frames = remote_frames;
+  p.T = 1;
+  DeviceScope dev_scope(b->device);
+  rb_status r = pace_reserve(b);
+  if (r != RB_OK) return r;
+  if (b->ts_on) {
+    r = ts_log_reserve(b, 1);
+    if (r != RB_OK) return r;
+    p.tick_log = b->ts_log;  // one row, consumed by every tick's own time-sync launch
+  }
+  b->ticked = true;
+  p.status = b->pace.view;  // parked sessions read as panicked: p2p_kernel returns before any store
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  if (b->prof) {
+    if (b->prof_used == b->prof_ev.size()) {
+      P2P_TRY(b, hipEventCreate(&e0));
+      P2P_TRY(b, hipEventCreate(&e1));
+      b->prof_ev.emplace_back(e0, e1);
+    }
+    e0 = b->prof_ev[b->prof_used].first;
+    e1 = b->prof_ev[b->prof_used].second;
+    P2P_TRY(b, hipEventRecord(e0, b->stream));
+  }
+  const dim3 grid((b->S + 255) / 256), block(256);
+  auto poll = IB == 1 ? poll_kernel_of<1>(b->P) : poll_kernel_of<4>(b->P);
+  const TimeSyncParams ts = b->ts_on ? b->ts : TimeSyncParams{};
+  // n_ticks one-tick sequences on the stream.  p2p_time_sync_kernel keeps a session's advantages in
+  // registers from entry to exit and ends its walk at the first unwritten row (a parked tick's), so
+  // it runs once per tick, on that tick's row; and it reads the view, not the status array, which
+  // does not have this tick's panics of the running sessions until p2p_unpark_kernel has run.
+  for (int32_t t = 0; t < n_ticks; ++t) {
+    const uint8_t* const mask = run_mask + static_cast<int64_t>(t) * b->S;
+    p.local_in = static_cast<const uint8_t*>(local_inputs) + static_cast<int64_t>(t) * local_stride;
+    p.upto = remote_upto + static_cast<int64_t>(t) * p.upto_stride;
+    hipLaunchKernelGGL(poll, grid, block, 0, b->stream, b->pace, mask, b->qs, static_cast<uint8_t*>(b->ring), b->status,
+                       b->counters, p.upto, p.remote_in, remote_frames, b->cfg.remote_delay, b->cfg.local_mask, ts, b->S,
+                       b->Spad);
+    P2P_TRY(b, hipGetLastError());
+    p.launch_clock = b->clock.next();
+    const hipError_t e = b->ops->launch_p2p(p, b->block, b->stream);
+    if (e != hipSuccess) return pfail(b, RB_DEVICE_ERROR, std::string("p2p launch: ") + hipGetErrorString(e));
+    if (b->ts_on) {
+      r = ts_launch(b, p, 1, b->pace.view);
+      if (r != RB_OK) return r;
+    }
+    hipLaunchKernelGGL(p2p_unpark_kernel, grid, block, 0, b->stream, b->pace.view, mask, b->status, b->S);
+    P2P_TRY(b, hipGetLastError());
+  }
+  if (e1) {
+    P2P_TRY(b, hipEventRecord(e1, b->stream));
+    ++b->prof_used;
+  }
+  return RB_OK;
+}
+
+rb_status rb_p2p_pace(rb_p2p* b, uint8_t* run_mask_dev) {
+  if (!b->ts_on) return pfail(b, RB_INVALID_REQUEST, kTsOff);
+  if (!run_mask_dev) return pfail(b, RB_INVALID_REQUEST, "rb_p2p_pace: missing run mask");
+  DeviceScope dev_scope(b->device);
+  rb_status r = pace_reserve(b);
+  if (r != RB_OK) return r;
+  hipLaunchKernelGGL(p2p_pace_kernel, dim3((b->S + 255) / 256), dim3(256), 0, b->stream, b->pace, b->ts.state, b->status,
+                     run_mask_dev, b->S, b->Spad);
+  P2P_TRY(b, hipGetLastError());
+  return RB_OK;
+}
+
+rb_status rb_p2p_read_pacing(rb_p2p* b, uint32_t* parked_ticks) {
+  if (!parked_ticks) return RB_OK;
+  DeviceScope dev_scope(b->device);
+  if (!b->pace.parked) {  // no paced tick yet
+    P2P_TRY(b, hipStreamSynchronize(b->stream));
+    std::memset(parked_ticks, 0, static_cast<size_t>(b->S) * 4);
+    return RB_OK;
+  }
+  std::vector<uint32_t> v;
+  rb_status r = read_rows(b, b->pace.parked, 1, v);
+  if (r != RB_OK) return r;
+  std::memcpy(parked_ticks, v.data(), static_cast<size_t>(b->S) * 4);
   return RB_OK;
 }
 

@@ -100,14 +100,17 @@ class P2PSession(_StreamOrdered):
                                                   ctypes.byref(o)))
         return bool(a.value), f.value, w.value, o.value
 
-    def run_ticks(self, local_inputs, remote_upto, remote_inputs) -> None:
+    def run_ticks(self, local_inputs, remote_upto, remote_inputs, run_mask=None) -> None:
         """T ticks: [poll_remote_clients, add_local_input for every local handle,
         advance_frame, handle_requests] x T in one device launch.
 
         local_inputs  [T, P, S] Input values (remote handles' rows ignored)
         remote_upto   [T, P, S] int32 newest delivered frame per remote handle
         remote_inputs [F, P, S] Input values by frame (local handles' rows ignored)
+        run_mask      None, or [T, S] uint8: 0 parks session s in tick t, which then only
+                      polls (rb_p2p_run_ticks_paced; T one-tick sequences on the stream)
         All torch CUDA tensors on the batch's device."""
+        import torch
         T = int(local_inputs.shape[0])
         assert tuple(local_inputs.shape[1:]) == (self.num_players, self.num_sessions)
         assert tuple(remote_upto.shape) == (T, self.num_players, self.num_sessions)
@@ -115,10 +118,19 @@ class P2PSession(_StreamOrdered):
         lp, lk = _dev_ptr(local_inputs)
         up, uk = _dev_ptr(remote_upto)
         rp, rk = _dev_ptr(remote_inputs)
+        keep = (lk, uk, rk)
+        if run_mask is not None:
+            assert run_mask.dtype == torch.uint8 and tuple(run_mask.shape) == (T, self.num_sessions)
+            mp, mk = _dev_ptr(run_mask)
+            keep += (mk,)
         cur = self._pre()
         stride = self.num_players * self.num_sessions * lk.element_size()
-        self._check(self._lib.rb_p2p_run_ticks(self._h, T, lp, stride, up, rp, int(remote_inputs.shape[0])))
-        self._post(cur, (lk, uk, rk))
+        if run_mask is None:
+            st = self._lib.rb_p2p_run_ticks(self._h, T, lp, stride, up, rp, int(remote_inputs.shape[0]))
+        else:
+            st = self._lib.rb_p2p_run_ticks_paced(self._h, T, lp, stride, up, rp, int(remote_inputs.shape[0]), mp)
+        self._post(cur, keep)
+        self._check(st)
 
     def run_ticks_packets(self, local_inputs, packets, lengths, start_frames, decode_status=None, acks=None) -> None:
         """T ticks fed by the peers' input packets (rb_p2p_run_ticks_packets):
@@ -174,9 +186,31 @@ class P2PSession(_StreamOrdered):
             raise InvalidRequest((self._lib.rb_p2p_last_error(self._h) or b"").decode())
         self._check(st)
 
-    def advance_frame(self, local_inputs, remote_upto, remote_inputs) -> None:
-        """One tick (run_ticks with T = 1): local_inputs [P, S], remote_upto [P, S]."""
-        self.run_ticks(local_inputs[None], remote_upto[None], remote_inputs)
+    def advance_frame(self, local_inputs, remote_upto, remote_inputs, run=None) -> None:
+        """One tick (run_ticks with T = 1): local_inputs [P, S], remote_upto [P, S];
+        run None, or [S] uint8: 0 parks the session for this tick."""
+        self.run_ticks(local_inputs[None], remote_upto[None], remote_inputs, None if run is None else run[None])
+
+    # -- pacing (ex_game_p2p.rs:80-122; DESIGN.md section 13)
+    def pace(self, out=None):
+        """The next tick's run mask from frames_ahead (rb_p2p_pace): a uint8 CUDA tensor [S],
+        stream ordered, no host copy.  A session that is ahead runs 10 ticks of every 11.
+        Needs enable_time_sync; `out` may be reused."""
+        import torch
+        if out is None:
+            out = torch.empty((self.num_sessions,), dtype=torch.uint8, device=f"cuda:{self._device}")
+        assert out.is_cuda and out.is_contiguous() and out.dtype == torch.uint8 and tuple(out.shape) == (self.num_sessions,)
+        cur = self._pre()
+        st = self._lib.rb_p2p_pace(self._h, ctypes.c_void_p(out.data_ptr()))
+        self._post(cur, (out,), outputs=True)
+        self._check(st)
+        return out
+
+    def parked_ticks(self):
+        """Ticks each session sat out since create, uint32 [S] (rb_p2p_read_pacing)."""
+        out = np.empty(self.num_sessions, np.uint32)
+        self._check(self._lib.rb_p2p_read_pacing(self._h, out.ctypes.data_as(ctypes.c_void_p)))
+        return out
 
     def status(self):
         """(rb_status [S], LoadGameState frame [S] (NULL_FRAME = no rollback),

@@ -593,6 +593,48 @@ rb_status rb_p2p_read_wait_recommendations(rb_p2p* b, uint32_t* counts, int32_t*
 /* For tests: the windows, out[2 local, remote][30][num_players][S].  Synchronises. */
 rb_status rb_p2p_debug_read_time_sync_windows(rb_p2p* b, int32_t* out);
 
+/* ---- Per-session pacing: the caller's frame loop of
+ * examples/ex_game/ex_game_p2p.rs:80-122, where poll_remote_clients runs on
+ * every iteration (:84), add_local_input and advance_frame only when the
+ * session's own accumulator says a frame is due (:107-122), and a session that
+ * is ahead stretches its frame time by 10% (:91-104).
+ *
+ * rb_p2p_run_ticks_paced is rb_p2p_run_ticks with a run mask: device uint8
+ * [n_ticks][S], 0 = parked.  A tick in which session s is parked runs
+ * poll_remote_clients for s (the deliveries of remote_upto / remote_inputs enter
+ * its input queues and connect status; with time sync on,
+ * update_local_frame_advantage of its running endpoints, protocol.rs:268-277)
+ * and nothing else: no add_local_input (its local inputs of that tick are
+ * ignored), no advance_frame, no request.  Its state, cells, frames, the
+ * status and request counts rb_p2p_read_status reports (those of its last
+ * advance_frame), its share of rb_p2p_totals, frames_ahead and the time-sync
+ * windows stay as they were.  input_queue.rs:181's assert fired by a parked
+ * poll (a session parked while deliveries go on for more than 128 frames)
+ * panics the session like a running tick's poll.  Running sessions do exactly
+ * what rb_p2p_run_ticks does.  run_mask == NULL is rb_p2p_run_ticks itself.
+ * A call of n_ticks is n_ticks one-tick sequences on the stream (pacing is for
+ * live play, one tick per call), each two small launches more than an unpaced
+ * one-tick call.  Sparse saving, desync detection, peers' connect-status
+ * reports, disconnects and time sync on or off all work.  RB_INVALID_REQUEST
+ * with nothing applied: a batch with the fan-out.  Packet-fed ticks have no
+ * paced form. */
+rb_status rb_p2p_run_ticks_paced(rb_p2p* b, int32_t n_ticks, const void* local_inputs, int64_t local_stride_bytes,
+                                 const int32_t* remote_upto, const void* remote_inputs, int32_t remote_frames,
+                                 const uint8_t* run_mask);
+
+/* The pacer: frames_ahead of every session into the next tick's run mask,
+ * run_mask_dev device uint8 [S], stream ordered, no host round trip.  The
+ * integer form of ex_game_p2p.rs:91-104 for a batch ticking at the nominal
+ * frame rate, with a per-session accumulator that starts at 0:
+ *   acc += 10; cost = frames_ahead > 0 ? 11 : 10; run = acc >= cost; if (run) acc -= cost;
+ * so a session never ahead runs every tick and a session held ahead runs 10 of
+ * every 11.  A panicked session gets 1.  RB_INVALID_REQUEST: time sync off. */
+rb_status rb_p2p_pace(rb_p2p* b, uint8_t* run_mask_dev);
+
+/* Ticks each session was parked in since create, parked_ticks [S] (counted by
+ * the paced ticks, whatever made their masks).  Synchronises. */
+rb_status rb_p2p_read_pacing(rb_p2p* b, uint32_t* parked_ticks);
+
 /* TimeSync::average_frame_advantage (time_sync.rs:30-39) from the windows' sums
  * for n host (local_sum, remote_sum) pairs: device < 0 on the host, else by a
  * kernel on that device (the same function, time_sync.hpp). */
