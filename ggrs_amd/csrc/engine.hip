@@ -618,7 +618,7 @@ rb_status launch_steady_run(rb_batch* b, const uint8_t* tick_inputs, int64_t str
   r.debug = b->cfg.reserved[0];
   r.pipe = b->pipe ? 1 : 0;
   r.lds_pad = b->lds_pad;
-  r.many_waves = static_cast<uint64_t>(b->Spad) * b->ops->lanes > 2ull * 64ull * b->simds ? 1u : 0u;
+  r.many_waves = many_waves_per_simd(b->Spad, b->ops->lanes, b->simds) ? 1u : 0u;
   r.launch_clock = b->clock.next();
   const bool timed = b->prof;
   LaunchEv ev;  // the kernel's own start / end (hipExtLaunchKernel), no marker packets around it

@@ -31,6 +31,7 @@
 #include "games.hpp"
 #include "planner.hpp"
 #include <type_traits>
+#include <utility>
 
 namespace rb {
 
@@ -1015,103 +1016,39 @@ struct GameOpsT final : GameOps {
                        reinterpret_cast<rb_checksum_report*>(out));
     return hipGetLastError();
   }
-  template <bool kSpec, bool kSparse, bool kNet, bool kMtf = false, bool kLog = false>
-  static hipError_t launch_p2p_as_m(const P2PParams& p, int grid, int block, hipStream_t st, const LaunchEv& ev) {
-    size_t lds = p2p_lds_bytes<G>(block);  // (the HBM-cell launches below)
-    if constexpr ((!kSpec || inlane_fan<G>()) && !kNet && p2p_lds_queue<G>()) {
-      // the snapshot ring in LDS (p2p_lds_cell_bytes) for launches of many ticks: it is copied in and
-      // written back whole, which short launches (the wire path's one tick per launch) do not repay;
-      // with the fan-out only for the in-kernel one (fanout_kernel reads the HBM cells between ticks)
-      // ... unless the batch puts more than two waves on a SIMD and the plain or sparse path can keep
-      // only the input ring in LDS (kQ below): the LDS cells (79 KiB per 256 threads) fit two
-      // workgroups per CU, kQ four (131,072 sessions, lag 1-4: 6.72 -> 5.25 us per tick; at 65,536
-      // sessions, two waves per SIMD, the LDS cells stay faster, 3.43 against 3.81)
-      constexpr bool kHasQ = (!kSpec || (RB_SPEC_Q && inlane_fan<G>())) && !kNet && G::kLanes > 1;
-      if (p2p_lds_cells<G>(p.W, block) && p.T >= kLdsCellsMinTicks && (!kSpec || !p.fan_generic) &&
-          !(kHasQ && p.many_waves)) {
-        // lane-asynchronous ticks (plain path and sparse saving) unless the batch asked for lock-step
-        // ticks; the fan-out runs lock-step ticks
-        auto k = (!p.sync_ticks && !kSpec) ? p2p_kernel<G, kSpec, kSparse, kNet, true, !kSpec, false, kMtf, false, false, kLog>
-                                           : p2p_kernel<G, kSpec, kSparse, kNet, true, false, false, kMtf, false, false, kLog>;
-        lds = p2p_lds_bytes<G, true>(block) + p2p_lds_cell_bytes<G>(block, p.W);
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           static_cast<int>(lds));
-        if (e != hipSuccess) return e;
-        return rb_launch(k, dim3(grid), dim3(block), static_cast<uint32_t>(lds), st, ev, p);
-      }
+  // p2p_kernel<G, V> for the variant v: instantiated for the variants p2p_choose can return for G
+  // (p2p_variant_reachable) and no others.  (The rule that launch_p2p_as, launch_p2p_as_l and
+  // launch_p2p_as_m held here is p2p_choose, p2p_variant.hpp.)
+  using P2PKernel = void (*)(const P2PParams);
+  template <uint32_t V>
+  static void p2p_pick(uint32_t v, P2PKernel& k) {
+    if constexpr (p2p_variant_reachable(p2p_traits<G>(), V)) {
+      if (v == V) k = p2p_kernel<G, V>;
     }
-    if constexpr ((!kSpec || (RB_SPEC_Q && inlane_fan<G>())) && !kNet && p2p_lds_queue<G>() && G::kLanes > 1) {
-      if (p.T >= kLdsQMinTicks && (!kSpec || (p.many_waves && !p.fan_generic))) {  // the input ring alone in LDS
-        auto k = p2p_kernel<G, kSpec, kSparse, kNet, false, false, false, kMtf, true, false, kLog>;
-        lds = p2p_lds_bytes<G, true>(block);
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           static_cast<int>(lds));
-        if (e != hipSuccess) return e;
-        return rb_launch(k, dim3(grid), dim3(block), static_cast<uint32_t>(lds), st, ev, p);
-      }
-    }
-    // live play, one tick per launch: the tick count compiled in (p2p_kernel kOne: 121 -> 99 VGPRs, no
-    // SGPR spills; 9.70 -> 9.59 us at 65,536 sessions, packet-fed 11.07 -> 10.45; r06_ab_one_tick.log)
-    if constexpr (!kSpec && !kNet) {
-      if (p.T == 1)
-        return rb_launch(p2p_kernel<G, kSpec, kSparse, kNet, false, false, false, kMtf, false, true, kLog>, dim3(grid),
-                         dim3(block), static_cast<uint32_t>(lds), st, ev, p);
-    }
-    return rb_launch(p2p_kernel<G, kSpec, kSparse, kNet, false, false, false, kMtf, false, false, kLog>, dim3(grid), dim3(block),
-                     static_cast<uint32_t>(lds), st, ev, p);
   }
-  // the fan-out's candidates: the alphabet itself when it has at most K values, else the queues'
-  // move-to-front lists (kMtf); ex_game (16 inputs) builds both, larger alphabets only the lists
-  template <bool kSpec, bool kSparse, bool kNet, bool kLog>
-  static hipError_t launch_p2p_as_l(const P2PParams& p, int grid, int block, hipStream_t st, const LaunchEv& ev) {
-    if constexpr (kSpec) {
-      if constexpr (InputAlphabet<G>::value > static_cast<uint32_t>(kSpecBranches))
-        return launch_p2p_as_m<kSpec, kSparse, kNet, true, kLog>(p, grid, block, st, ev);
-      else if (InputAlphabet<G>::value > static_cast<uint32_t>(p.fan_k))
-        return launch_p2p_as_m<kSpec, kSparse, kNet, true, kLog>(p, grid, block, st, ev);
-    }
-    return launch_p2p_as_m<kSpec, kSparse, kNet, false, kLog>(p, grid, block, st, ev);
-  }
-  // time sync on (P2PParams::tick_log; never a packet-fed launch, which launch_p2p has taken by
-  // now): the instantiations that write the tick log (p2p_kernel kLog)
-  template <bool kSpec, bool kSparse, bool kNet>
-  static hipError_t launch_p2p_as(const P2PParams& p, int grid, int block, hipStream_t st, const LaunchEv& ev) {
-    if (p.tick_log) return launch_p2p_as_l<kSpec, kSparse, kNet, true>(p, grid, block, st, ev);
-    return launch_p2p_as_l<kSpec, kSparse, kNet, false>(p, grid, block, st, ev);
+  template <uint32_t... V>
+  static P2PKernel p2p_instance(uint32_t v, std::integer_sequence<uint32_t, V...>) {
+    P2PKernel k = nullptr;
+    const int each[] = {(p2p_pick<V>(v, k), 0)...};
+    (void)each;
+    return k;
   }
   hipError_t launch_p2p(const P2PParams& p, int block, hipStream_t st, const LaunchEv& ev) const override {
     const int grid = (p.Spad * G::kLanes + block - 1) / block;
-    if (p.packets) {  // packet-fed ticks (rb_p2p_run_ticks_packets: the plain path, lock-step ticks)
-      size_t lds = p2p_lds_bytes<G>(block);
-      if constexpr (p2p_lds_queue<G>()) {
-        if (p2p_lds_cells<G>(p.W, block) && p.T >= kLdsCellsMinTicks) {
-          auto k = p2p_kernel<G, false, false, false, true, false, true>;
-          lds = p2p_lds_bytes<G, true>(block) + p2p_lds_cell_bytes<G>(block, p.W);
-          hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                             static_cast<int>(lds));
-          if (e != hipSuccess) return e;
-          return rb_launch(k, dim3(grid), dim3(block), static_cast<uint32_t>(lds), st, ev, p);
-        }
-      }
-      if (p.T == 1)  // one tick per launch (kOne, above)
-        return rb_launch(p2p_kernel<G, false, false, false, false, false, true, false, false, true>, dim3(grid),
-                         dim3(block), static_cast<uint32_t>(lds), st, ev, p);
-      return rb_launch(p2p_kernel<G, false, false, false, false, false, true>, dim3(grid), dim3(block),
-                       static_cast<uint32_t>(lds), st, ev, p);
+    const P2PLaunchFacts f{p.T, p.W, block, p.packets != nullptr, p.sparse != 0, p.spec_on != 0, p.fan_generic != 0,
+                           p.fan_k, p.sync_ticks != 0, p.many_waves != 0, p.tick_log != nullptr, p.ds.interval > 0,
+                           p.peer.on != 0};
+    const P2PChoice c = p2p_choose(p2p_traits<G>(), f);
+    const P2PKernel k = p2p_instance(c.variant, std::make_integer_sequence<uint32_t, kP2PVariants>{});
+    if (!k) return hipErrorNotSupported;  // (p2p_variant_reachable admits everything p2p_choose returns)
+    if (c.variant & (kP2PLdsC | kP2PQ)) {
+      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                         static_cast<int>(c.lds));
+      if (e != hipSuccess) return e;
     }
-    if (p.ds.interval > 0 || p.peer.on) {  // desync detection / peers' connect-status reports on
-      if (p.sparse)  // sparse saving and the fan-out exclude each other (rb_p2p_create)
-        return launch_p2p_as<false, true, true>(p, grid, block, st, ev);
-      if (kFanout && p.spec_on && !p.peer.on)  // the fan-out assumes connected queues
-        return launch_p2p_as<kFanout, false, true>(p, grid, block, st, ev);
-      return launch_p2p_as<false, false, true>(p, grid, block, st, ev);
-    }
-    if (p.sparse) return launch_p2p_as<false, true, false>(p, grid, block, st, ev);
-    if (kFanout && p.spec_on) return launch_p2p_as<kFanout, false, false>(p, grid, block, st, ev);
-    return launch_p2p_as<false, false, false>(p, grid, block, st, ev);
+    return rb_launch(k, dim3(grid), dim3(block), static_cast<uint32_t>(c.lds), st, ev, p);
   }
-  // fan-out: one lane per player (ex_game) or one wave per session (the brawler), 1-byte inputs
-  static constexpr bool kFanout = ((G::kLanes > 1 && G::kLanes <= 4) || G::kLanes == 64) && G::kInputBytes == 1;
+  static constexpr bool kFanout = p2p_traits<G>().fanout;
   hipError_t launch_fanout(const FanParams& p, int block, hipStream_t st) const override {
     if constexpr (kFanout) {
       const int grid = (p.Spad * kSpecBranches * G::kLanes + block - 1) / block;

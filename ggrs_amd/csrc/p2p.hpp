@@ -31,6 +31,7 @@
 #include <hip/hip_runtime.h>
 
 #include "games.hpp"
+#include "p2p_variant.hpp"
 
 namespace rb {
 
@@ -126,12 +127,7 @@ constexpr int32_t kWireOk = 0, kWireNothing = 1, kWirePanic = -1, kWireGap = -2;
 // executed work: AdvanceFrames, SaveGameStates, LoadGameStates, rollbacks
 // replaced by a speculative branch select, branch frames presimulated
 enum : int { ST_ADV = 0, ST_SAVE = 1, ST_LOAD = 2, ST_SELECT = 3, ST_BRANCH = 4, ST_COUNT = 5 };
-// Speculative fan-out: branch k holds candidate input cand[k] for one remote
-// player over its unconfirmed frames.  Up to kSpecBranches
-// candidates: the game's whole input alphabet when it has at most that many
-// values (ex_game's 4 bits: cand[k] = k), else the K most likely values
-// (fan_candidates below).
-constexpr int kSpecBranches = 16;
+// (the speculative fan-out's kSpecBranches: p2p_variant.hpp)
 // spec_meta rows: first speculated frame (base), frame the branch states are at
 // (end), speculated handle, valid flag, then the 16 candidate inputs (1-byte
 // inputs, 4 per row; 0xFF..: no branch) the branches presimulated
@@ -418,7 +414,7 @@ struct P2PParams {
   uint32_t local_mask;
   int32_t sparse;
   int32_t sync_ticks;  // 1: lock-step ticks on the plain path too (no kAsync; A/B and tests)
-  int32_t many_waves;  // the batch puts more than two waves on a SIMD of this device (launch_p2p_as_m)
+  int32_t many_waves;  // the batch puts more than two waves on a SIMD of this device (many_waves_per_simd)
   DesyncParams ds;
   PeerParams peer;
   // kWire (rb_p2p_run_ticks_packets): the remote inputs arrive as the peers'
@@ -643,67 +639,8 @@ struct LdsRing {
     col[static_cast<unsigned>(f & (kQueueLen - 1)) * row] = static_cast<uint8_t>(v);
   }
 };
-// LDS queues: 1-byte inputs, one player per lane (ex_game lane per player, the brawler).
-template <class G>
-constexpr bool p2p_lds_queue() {
-  return G::kInputBytes == 1 && (G::kLanes > 1 || G::kPlayers == 1);
-}
-// ... in a launch whose snapshot ring is (kLdsC) or is not in LDS.  Launches of
-// few ticks keep the snapshot ring in HBM, and the input ring too: filling the
-// LDS copy (byte loads in dependent rounds) and writing it back cost more than
-// the handful of ring reads a short launch makes (measured, one tick per
-// launch at 65,536 sessions: 14.8 -> 13.1 us, the packet-fed tick 18.9 -> 16.7).
-#ifndef RB_SHORT_HBM_RING
-#define RB_SHORT_HBM_RING 1  // 0: the LDS input ring in every launch (A/B builds)
-#endif
-template <class G, bool kLdsC>
-constexpr bool p2p_lds_queue_in() {
-  return p2p_lds_queue<G>() && (kLdsC || !RB_SHORT_HBM_RING);
-}
-template <class G, bool kLdsC = false>
-constexpr size_t p2p_lds_bytes(int block) {
-  return p2p_lds_queue_in<G, kLdsC>() ? static_cast<size_t>(kQueueLen) * static_cast<size_t>(block) : 0;
-}
-// The snapshot ring in LDS (p2p_kernel kLdsC): for the launch, the W cells
-// (words [W][NWL][block], frame tags and checksums [W][block / kLanes]) live
-// after the queue in LDS; the launch loads them from HBM first and writes
-// them back last.  Every SaveGameState and LoadGameState inside is an LDS
-// access, and the tick loop issues no global store at all: CDNA's vmcnt
-// retires loads and stores in issue order, so with a tick's snapshot stores
-// in flight, waiting for the next tick's prefetched deliveries would wait for
-// the stores too (the compiler cannot count stores issued in a loop of
-// data-dependent length and drains the counter).  Up to kLdsCellsMaxW cells:
-// at W = 8, 512 threads per CU (two waves per SIMD) take 156 KiB of the 160.
-constexpr int kLdsCellsMaxW = 8;
-template <class G>
-constexpr size_t p2p_lds_cell_bytes(int block, int W) {
-  return static_cast<size_t>(W) * (static_cast<size_t>(G::NWL) * 4 * block +
-                                   (4 + sizeof(typename G::CS)) * static_cast<size_t>(block / G::kLanes));
-}
-// ... when the queue and the cells of a block fit half of a CU's 160 KiB (two
-// blocks per CU): ex_game's 40 B cells do (79 KiB at 256 threads, W = 8), the
-// brawler's 8 KiB cells do not and stay in HBM.
-constexpr size_t kLdsPerBlockMax = 80 * 1024;
-#ifndef RB_LDS_CELLS_MIN_TICKS
-#define RB_LDS_CELLS_MIN_TICKS 24
-#endif
-// launches of fewer ticks keep the cells in HBM (and lock-step ticks): copying the
-// ring in and out costs more than it saves below about 24 ticks (measured: HBM
-// cells 4.8 us per tick at 16 ticks per launch, LDS cells 4.1 at 32)
-constexpr int kLdsCellsMinTicks = RB_LDS_CELLS_MIN_TICKS;
-// Launches of kLdsQMinTicks up to kLdsCellsMinTicks ticks keep the cells in HBM but the input ring
-// in LDS (p2p_kernel kQ; plain path and sparse saving, ex_game's lane-per-player layout).  Measured
-// at 65,536 sessions, us per tick (HBM ring / LDS ring / LDS cells): 2 ticks per launch 7.6 / 8.0 /
-// 12.7, 4: 6.34 / 6.08 / 8.44, 8: 5.57 / 5.02 / 5.97, 16: 5.07 / 4.36 / 4.55 (round 4, interleaved A/B, tools/ab.py).
-#ifndef RB_LDSQ_MIN_TICKS
-#define RB_LDSQ_MIN_TICKS 4
-#endif
-constexpr int kLdsQMinTicks = RB_LDSQ_MIN_TICKS;
-template <class G>
-constexpr bool p2p_lds_cells(int W, int block) {
-  return p2p_lds_queue<G>() && W <= kLdsCellsMaxW &&
-         p2p_lds_bytes<G, true>(block) + p2p_lds_cell_bytes<G>(block, W) <= kLdsPerBlockMax;
-}
+// Which launches keep the input ring, and the snapshot ring, in LDS: p2p_variant.hpp (p2p_lds_queue,
+// p2p_lds_cells, kLdsCellsMinTicks, kLdsQMinTicks) and p2p_traits<G>() below.
 
 // input_queue.rs:167-204 add_input_by_frame (Cn: the game's InputCanon, for the fan-out's list)
 template <class Cn, class R>
@@ -815,6 +752,17 @@ constexpr bool inlane_fan() {
   if constexpr (IndepPlayers<G>::value) return G::kLanes > 1 && G::kLanes <= 4 && !G::kUsesStatus && G::kInputBytes == 1;
   else return false;
 }
+// What p2p_choose (p2p_variant.hpp) reads of a game.  The two-launch fan-out (fanout_kernel): one
+// lane per player (ex_game) or one wave per session (the brawler), 1-byte inputs.
+template <class G>
+constexpr P2PTraits p2p_traits() {
+  return {G::kLanes, G::kPlayers, G::kInputBytes, G::NWL, static_cast<int>(sizeof(typename G::CS)), InputAlphabet<G>::value,
+          ((G::kLanes > 1 && G::kLanes <= 4) || G::kLanes == 64) && G::kInputBytes == 1, inlane_fan<G>()};
+}
+template <class G, bool kLdsC>
+constexpr bool p2p_lds_queue_in() {
+  return p2p_lds_queue_in(p2p_traits<G>(), kLdsC);
+}
 #ifndef RB_FAN_GROUP
 #define RB_FAN_GROUP 4  // A/B (tools/ab.py, round 4): 3 measured the same at C4 (206 VGPRs, still 2 waves per
 #endif                  // SIMD); 3 with a 3-waves cap (168 VGPRs, 160 B spilled) 8% slower
@@ -856,12 +804,7 @@ constexpr int kFanGroup = RB_FAN_GROUP;  // chains a lane advances together (ind
 #ifndef RB_P2P_WAVES_PER_EU
 #define RB_P2P_WAVES_PER_EU 1  // >1: ask the compiler for that many waves per SIMD (VGPR cap; A/B builds)
 #endif
-// RB_SPEC_Q: the in-kernel fan-out of a batch with more than two waves per SIMD keeps its cells in HBM
-// and only the input ring in LDS (kQ), capped at RB_SPEC_Q_WAVES waves per SIMD, instead of the LDS
-// snapshot ring's two workgroups per CU
-#ifndef RB_SPEC_Q
-#define RB_SPEC_Q 0
-#endif
+// (RB_SPEC_Q, p2p_variant.hpp: the in-kernel fan-out with kQ) is compiled for this many waves per SIMD
 #ifndef RB_SPEC_Q_WAVES
 #define RB_SPEC_Q_WAVES 3
 #endif
@@ -891,22 +834,30 @@ __device__ uint64_t rb_p2p_phase[8 * 4096];
   do {           \
   } while (0)
 #endif
-template <class G, bool kSpec, bool kSparse, bool kNet, bool kLdsC, bool kAsync, bool kWire = false, bool kMtf = false,
-          bool kQ = false, bool kOne = false, bool kLog = false>
+// waves per SIMD a variant (P2PFlag set) is compiled for
+constexpr int p2p_waves_per_eu(uint32_t V) {
+  const bool kSpec = V & kP2PSpec, kNet = V & kP2PNet, kLdsC = V & kP2PLdsC, kQ = V & kP2PQ, kOne = V & kP2POne;
+  return kOne ? RB_P2P_ONE_WAVES : (kQ && kSpec) ? RB_SPEC_Q_WAVES : (kQ || (!kLdsC && !kSpec && !kNet)) ? RB_P2P_SHORT_WAVES : RB_P2P_WAVES_PER_EU;
+}
+// V: the variant, a P2PFlag set (p2p_variant.hpp), unpacked into kSpec .. kLog below.
+template <class G, uint32_t V>
 // kLog: the launch writes the tick log (P2PParams::tick_log, time sync on).  A template flag and not
 // a null check: the instantiations without it keep their registers (most sit at their SGPR or VGPR
 // caps, profiles/time_sync_resource_usage.txt).
 // kQ (the input ring alone in LDS, 32 KiB per 256 threads) is capped at 128 VGPRs: with the cells in
 // HBM four workgroups fit a CU, so batches of more than two waves per SIMD run four resident instead
-// of the LDS-cell kernel's two (kernels.hpp launch_p2p_as_m).
+// of the LDS-cell kernel's two (p2p_choose).
 // The launches that keep the cells in HBM on the plain / sparse path (kQ, and the one-tick launches
 // of live play) are capped at 128 VGPRs the same way: four waves per SIMD once a batch has them.
 __global__ void __launch_bounds__(256)
-__attribute__((amdgpu_waves_per_eu(kOne ? RB_P2P_ONE_WAVES : (kQ && kSpec) ? RB_SPEC_Q_WAVES : (kQ || (!kLdsC && !kSpec && !kNet)) ? RB_P2P_SHORT_WAVES : RB_P2P_WAVES_PER_EU)))
+__attribute__((amdgpu_waves_per_eu(p2p_waves_per_eu(V))))
 p2p_kernel(const P2PParams p) {
-  static_assert(!kAsync || (kLdsC && !kSpec && !kNet), "lane-asynchronous ticks: plain or sparse path, LDS cells");
-  static_assert(!kWire || (!kSpec && !kSparse && !kNet && !kAsync), "packet-fed ticks: the plain lock-step path");
-  static_assert(!(kWire && kLog), "the tick log shares its parameter word with the packet-fed launches' pk_status");
+  constexpr bool kSpec = V & kP2PSpec, kSparse = V & kP2PSparse, kNet = V & kP2PNet, kLdsC = V & kP2PLdsC,
+                 kAsync = V & kP2PAsync, kWire = V & kP2PWire, kMtf = V & kP2PMtf, kQ = V & kP2PQ, kOne = V & kP2POne,
+                 kLog = V & kP2PLog;
+  static_assert(p2p_variant_valid(V), "lane-asynchronous ticks need the LDS cells, which the fan-out's and the network's "
+                                      "HBM reads exclude; packet-fed ticks are plain, lock-step and unlogged; one-tick "
+                                      "launches keep the cells in HBM");
   using InRec = typename G::InRec;
   using CS = typename G::CS;
   constexpr int NW = G::NWL;
@@ -919,8 +870,7 @@ p2p_kernel(const P2PParams p) {
   const int lane = static_cast<int>(g % L);
   const bool lead = lane == 0;
   // kOne: the launches of one tick (live play), the tick count a compile-time 1, so the tick loop
-  // and the next tick's prefetch compile away (kernels.hpp launch_p2p_as_m)
-  static_assert(!kOne || (!kLdsC && !kAsync && !kQ), "one-tick launches keep the cells in HBM");
+  // and the next tick's prefetch compile away (p2p_choose)
   const int T = kOne ? 1 : p.T;
   if (p.launch_clock) launch_clock_put(p.launch_clock, g / 64u, 0u);
   if (s >= static_cast<unsigned>(p.S)) return;  // whole lane groups leave together

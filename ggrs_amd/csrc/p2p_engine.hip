@@ -542,7 +542,7 @@ P2PParams base_params(const rb_p2p* b) {
   p.local_mask = b->cfg.local_mask;
   p.sparse = b->cfg.sparse_saving != 0;
   p.sync_ticks = b->sync_ticks ? 1 : 0;
-  p.many_waves = static_cast<uint64_t>(b->Spad) * b->ops->lanes > 2ull * 64ull * b->simds ? 1 : 0;
+  p.many_waves = many_waves_per_simd(b->Spad, b->ops->lanes, b->simds) ? 1 : 0;
   p.fan_generic = b->fan_generic ? 1 : 0;
   p.fan_k = b->cfg.fanout_candidates;
   p.spec_on = b->fanout ? 1 : 0;

@@ -3,9 +3,12 @@
 
     python3 tools/resource_report.py > profiles/spectator_resource_usage.txt
 
-With --against REPORT (a report of another commit, made the same way) every p2p_kernel line is
-followed by how it compares: the instantiation of the same name there, where a trailing
-", false" template argument this commit added (a flag that is off) is dropped from the name.
+A p2p_kernel instantiation is printed with its variant's flags by name (p2p_variant.hpp P2PFlag),
+p2p_kernel<ExGame<2, true>, LdsC|Async|Log>.  With --against REPORT (a report of another commit,
+made the same way) every p2p_kernel line is followed by how it compares with the instantiation of
+the same flags there; a report from when the flags were ten positional bool template arguments
+(missing trailing ones false) is read as the same names.  Instantiations only the other report has
+are listed at the end.
 
     python3 tools/resource_report.py --against parent_report.txt ops_exgame_p2.hip ...
 
@@ -27,7 +30,18 @@ if "--against" in sys.argv:
     i = sys.argv.index("--against")
     AGAINST = sys.argv[i + 1]
     del sys.argv[i:i + 2]
+P2P_FLAGS = ["Spec", "Sparse", "Net", "LdsC", "Async", "Wire", "Mtf", "Q", "One", "Log"]  # bit 0 .. 9, the old argument order
 TUS = sys.argv[1:] or ["ops_exgame_p2.hip", "ops_exgame_p3.hip", "ops_exgame_p4.hip", "ops_brawler_p2.hip", "ops_stub.hip"]
+
+
+def p2p_name(n):
+    """p2p_kernel<G, 24u> or p2p_kernel<G, false, false, false, true, true> as p2p_kernel<G, LdsC|Async>."""
+    m = re.fullmatch(r"(p2p_kernel<.*?), (\d+)u>", n) or re.fullmatch(r"(p2p_kernel<.*?)((?:, (?:true|false))+)>", n)
+    if not m:
+        return n
+    on = ([(int(m.group(2)) >> i) & 1 for i in range(len(P2P_FLAGS))] if m.group(2).isdigit()
+          else [a == "true" for a in m.group(2)[2:].split(", ")])
+    return f"{m.group(1)}, {'|'.join(f for f, b in zip(P2P_FLAGS, on) if b) or '0'}>"
 
 
 def load_report(path):
@@ -38,7 +52,7 @@ def load_report(path):
             tu = line[3:].strip()
         elif line.strip() and not line.startswith("#"):
             f = line.split(None, 8)
-            out[tu, f[8].strip()] = tuple(int(x) for x in f[:8])
+            out[tu, p2p_name(f[8].split("   [")[0].strip())] = tuple(int(x) for x in f[:8])
     return out
 
 
@@ -75,11 +89,11 @@ def main():
             n = n.replace("(anonymous namespace)::", "")
             n = n[5:] if n.startswith("void ") else n
             n = n.replace("rb::", "")
-            n = n.split("(")[0]
+            n = p2p_name(n.split("(")[0])
             vals = tuple(r.get(k, 0) for k in ("v", "a", "s", "ss", "vs", "sc", "o", "l"))
             note = ""
             if base is not None and n.startswith("p2p_kernel<"):
-                old = base.get((tu, n)) or (base.get((tu, n[:-len(", false>")] + ">")) if n.endswith(", false>") else None)
+                old = base.pop((tu, n), None)
                 if old is None:
                     added += 1
                     note = "   [new]"
@@ -92,7 +106,11 @@ def main():
             print(f"  {vals[0]:4d} {vals[1]:4d} {vals[2]:4d} {vals[3]:10d} {vals[4]:10d} "
                   f"{vals[5]:14d} {vals[6]:10d} {vals[7]:6d}  {n}{note}")
     if base is not None:
-        print(f"# p2p_kernel instantiations against {os.path.basename(AGAINST)}: {same} unchanged, {changed} changed, {added} new")
+        gone = sorted(k for k in base if k[0] in TUS and k[1].startswith("p2p_kernel<"))
+        for tu, n in gone:
+            print(f"# only in {os.path.basename(AGAINST)}: {tu} {n}")
+        print(f"# p2p_kernel instantiations against {os.path.basename(AGAINST)}: {same} unchanged, {changed} changed, "
+              f"{added} new" + (f", {len(gone)} GONE" if gone else ""))
 
 
 if __name__ == "__main__":
