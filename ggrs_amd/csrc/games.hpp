@@ -328,6 +328,52 @@ struct ExGame {
       pr.rot[j][N] = rot;
     }
   }
+  // ---- the prepared window carried from one fused tick to the next (kernels.hpp steady_kernel).
+  // Tick t+1 loads the cell tick t stored at its frame 1, and its input window is tick t's moved
+  // on by one confirmed input.  So frames 0 .. N-2 of its window are frames 1 .. N-1 of tick t's:
+  // the same rotations, the same thrust, bit for bit.  `extend` moves the window down by one frame
+  // and computes the one new frame with the operations `prepare` performs for a frame, in their
+  // in-range forms.  `carry_ok` is what that takes: the loaded rotation is the carried one on the
+  // bits (the window still follows from the loaded cell), and the new frame starts from a rotation
+  // in [+0, 6.5) (in_range).  The kernel asks it of the whole wave and runs `prepare` otherwise.
+  static constexpr bool kHasCarry = true;
+  // Largest check distance that carries.  The window is 3 N + 1 words per player of the lane
+  // (N = CD + 1): 52 VGPRs at CD = 16 with one player per lane, less than the 4 x 17 words of the
+  // decoded input window it replaces, so every fused check distance fits without scratch.
+  static constexpr int kCarryMaxCD = 16;
+  template <int N>
+  __device__ static bool carry_ok(const uint32_t (&w)[NWL], const Prep<N>& pr) {
+    bool ok = true;
+#pragma unroll
+    for (int j = 0; j < kPlayersPerLane; ++j) {
+      ok &= w[5 * j + 4] == __float_as_uint(pr.rot[j][1]);
+      ok &= __float_as_uint(pr.rot[j][N]) < 0x40D00000u;  // +0 <= r < 6.5f
+    }
+    return ok;
+  }
+  template <int N>
+  __device__ static void extend(Prep<N>& pr, const Dec& d) {
+    pr.xlim = kWidth;  // set per tick as in `prepare`: two moves, and no registers held across ticks
+    pr.ylim = kHeight;
+    asm("" : "+v"(pr.xlim), "+v"(pr.ylim));
+#pragma unroll
+    for (int j = 0; j < kPlayersPerLane; ++j) {
+#pragma unroll
+      for (int k = 0; k + 1 < N; ++k) {
+        pr.tx[j][k] = pr.tx[j][k + 1];
+        pr.ty[j][k] = pr.ty[j][k + 1];
+      }
+#pragma unroll
+      for (int k = 0; k < N; ++k) pr.rot[j][k] = pr.rot[j][k + 1];
+      const float rot = pr.rot[j][N - 1];
+      const SinCos sc = sincosf_glibc<true>(rot, nullptr);
+      const float tx = d.sp[j] * sc.c, ty = d.sp[j] * sc.s;
+      pr.tx[j][N - 1] = thrust_or_neg_zero(d.thm(j), tx);
+      pr.ty[j][N - 1] = thrust_or_neg_zero(d.thm(j), ty);
+      const float r1 = rem_euclid_near<true>(rot + d.rd[j], 2.0f * kPi);
+      pr.rot[j][N] = __uint_as_float(bit_select(d.rom(j), __float_as_uint(r1), __float_as_uint(rot)));
+    }
+  }
   // AdvanceFrame k of the prepared tick: friction, thrust, speed clamp, position.
   template <int N>
   __device__ static void advance_prepared(uint32_t (&w)[NWL], const Prep<N>& pr, int k) {

@@ -265,10 +265,16 @@ template <class G>
 struct HasFast<G, std::void_t<decltype(G::kHasFast)>> {
   static constexpr bool value = G::kHasFast;
 };
-template <class G, class Pr>
-__device__ __forceinline__ void advance_fast(uint32_t (&w)[G::NWL], const Pr& pr, int k, uint32_t& special) {
-  if constexpr (HasFast<G>::value) G::advance_prepared_fast(w, pr, k, special);
-}
+// G::kHasCarry at check distance CD (games.hpp ExGame::extend / carry_ok: the prepared window of
+// a fused tick carried into the next one), false when not declared or above G::kCarryMaxCD
+template <class G, int CD, class = void>
+struct HasCarry {
+  static constexpr bool value = false;
+};
+template <class G, int CD>
+struct HasCarry<G, CD, std::void_t<decltype(G::kHasCarry)>> {
+  static constexpr bool value = G::kHasPrep && G::kHasCarry && CD <= G::kCarryMaxCD;
+};
 // One AdvanceFrame{inputs} (State::advance, ex_game.rs:259-321) for the
 // kernels that run frames one at a time (tick_kernel, p2p_kernel, the fan-out).
 // (Round 3 measured a branch-free form with a wave-wide redo here: neutral on
@@ -422,6 +428,8 @@ __global__ void __launch_bounds__(256) tick_kernel(const KParams p) {
 //    through register windows; the one new input per tick comes from the
 //    read-only per-tick input buffer, never from a ring entry this launch
 //    wrote.
+//  * games with G::kHasCarry (ex_game) carry the prepared window of the tick (rotations and
+//    thrust of its CD+1 frames) into the next tick instead of the inputs: see the loop head.
 // The host bookkeeping runs per tick as usual; only ticks whose lowered
 // program has exactly this shape are fused.
 struct RunParams {
@@ -496,14 +504,6 @@ struct DecSel<G, true> {
 };
 template <class G>
 using DecOf = typename DecSel<G>::type;
-// RB_STEADY_FAST (RB_EXPERIMENTS builds only): the branch-free form with the tick redo, measured
-// slower (269 vs 220 us per 50 ticks, round 3); never compiled into the product library.
-#if RB_EXPERIMENTS && defined(RB_STEADY_FAST_AB)
-#define RB_STEADY_FAST 1
-#else
-#define RB_STEADY_FAST 0
-#endif
-
 // kExp: attribution experiments (RunParams::debug knobs, tools/exp_steady.py);
 // instantiated only in builds made with RB_EXPERIMENTS=1, never in the product.
 #ifndef RB_STEADY_WAVES_PER_EU
@@ -518,7 +518,10 @@ using DecOf = typename DecSel<G>::type;
 #if RB_WAVE_CLOCK
 __device__ uint64_t rb_wave_clock[4 * 8192];
 #endif
-template <class G, int CD, bool kExp>
+// kCarryOn = false: the form for launches of one tick, which have no second tick to carry the
+// prepared window into: every load of the tick is issued in the prologue and the window prepared
+// from the decoded input window, as for games without the trait.
+template <class G, int CD, bool kExp, bool kCarryOn = true>
 __global__ void __launch_bounds__(256)
 #if RB_STEADY_WAVES_PER_EU > 0
 __attribute__((amdgpu_waves_per_eu(1, RB_STEADY_WAVES_PER_EU)))
@@ -594,16 +597,25 @@ steady_kernel(const RunParams p) {
   int f0 = p.c0 - CD;
   uint32_t w[NW];
   load_words<NW>(p.snap + slot_of(f0) * slot_words, static_cast<int>(Gpad), static_cast<int>(g), w);
-  InRec win[CD + 1];  // inputs of frames f0 .. f0+CD
+  // kCarry: the prepared window (rotations and thrust of the CD+1 frames) lives through the
+  // launch and moves on by one frame per tick (games.hpp ExGame::extend); see the loop head.
+  // Of the input window these games keep only the newest frame's input in registers (win[CD]):
+  // the others are read again where the whole window is prepared (the first tick of a launch).
+  constexpr bool kCarry = HasCarry<G, CD>::value && !kExp && kCarryOn;
+  InRec win[CD + 1] = {};  // inputs of frames f0 .. f0+CD
+  if constexpr (!kCarry) {
 #pragma unroll
-  for (int k = 0; k <= CD; ++k) win[k] = input_of_frame(f0 + k);
-  // the phase-split games read the window decoded (games.hpp ExGame::Dec), each
+    for (int k = 0; k <= CD; ++k) win[k] = input_of_frame(f0 + k);
+  }
+  // the other phase-split games read the window decoded (games.hpp ExGame::Dec), each
   // input once, as it enters the window
+  constexpr bool kDecWin = G::kHasPrep && !kCarry && !kExp;
   [[maybe_unused]] DecOf<G> dec[CD + 1];
-  if constexpr (G::kHasPrep) {
+  if constexpr (kDecWin) {
 #pragma unroll
     for (int k = 0; k <= CD; ++k) dec[k] = G::decode(win[k], lane);
   }
+  [[maybe_unused]] PrepOf<G, CD + 1> prep;  // (kCarry)
   CS fsw[NF];  // SyncTest first-seen checksums of frames f0+1 .. f0+CD-1
 #pragma unroll
   for (int k = 1; k < CD; ++k) fsw[k - 1] = fsa[slot_of(f0 + k) * Spad + s];
@@ -622,8 +634,10 @@ steady_kernel(const RunParams p) {
   // store of the previous tick.
 #pragma unroll
   for (int i = 0; i < NW; ++i) settle(w[i]);
+  if constexpr (!kCarry) {
 #pragma unroll
-  for (int k = 0; k <= CD; ++k) settle(win[k]);
+    for (int k = 0; k <= CD; ++k) settle(win[k]);
+  }
 #pragma unroll
   for (int k = 0; k + 1 < CD; ++k) settle(fsw[k]);
   settle(newin);
@@ -651,23 +665,39 @@ steady_kernel(const RunParams p) {
     // one scalar modulo per tick instead of a divisibility test per save
     [[maybe_unused]] const int kp = G::kDisplay ? (100 - f0 % 100) % 100 : -1;
     uint32_t wn[NW];  // next tick's LoadGameState(c+1-CD), loaded right after this tick saves it
+    if constexpr (kCarry) {
+      // The prepared window.  The cell this tick loaded is the one the same lanes stored at frame 1
+      // of the previous tick, and the input window moved on by one, so frames 0 .. CD-1 of this
+      // tick's window are frames 1 .. CD of the last one's: only the newest frame is computed.
+      // The guard keeps that a fact about memory and not about the code: the window is carried only
+      // when every lane's loaded rotation is the carried one on the bits (G::carry_ok); otherwise,
+      // and at the first tick of a launch, the whole window is prepared from the loaded cell (one
+      // copy of that code: inlined a second time it set the kernel's register count).
+      if (t != 0 && __all(G::carry_ok(w, prep))) {
+        G::extend(prep, G::decode(win[CD], lane));
+      } else {
+        DecOf<G> d[CD + 1];
+#pragma unroll
+        for (int k = 0; k <= CD; ++k) d[k] = G::decode(input_of_frame(f0 + k), lane);
+        if (__all(G::in_range(w)))
+          G::template prepare<true, CD + 1>(w, d, prep, &p.counters[1]);
+        else
+          G::template prepare<false, CD + 1>(w, d, prep, &p.counters[1]);
+      }
+    }
     // The tick's steps, instantiated twice: with the game's out-of-line range
     // checks compiled out when the whole wave's loaded state is in range
-    // (G::in_range, decided once per tick), and the general form otherwise.
+    // (G::in_range, decided once per tick), and the general form otherwise;
+    // once for the games that carry the prepared window, whose steps hold no range check.
     // Checksums are whole-session values present in every lane of the group
     // (group_sum), so the checksum stores are issued by every lane: the lanes
     // of a session write the same value to the same address, and no exec-mask
     // branch splits the tick into separately scheduled blocks.
-    // kFast (in-range ticks of a game with G::kHasFast): the branch-free AdvanceFrame, whose
-    // flagged lanes (operands outside its short division sequence) make the wave redo the tick
-    // in the general form below; returns this lane's flag.
-    auto steps = [&](auto in_range_tag, auto fast_tag) __attribute__((always_inline)) -> uint32_t {
+    // `pr`: the prepared window the steps read: the carried one, or one of this tick alone.
+    auto steps = [&](auto in_range_tag, auto& pr) __attribute__((always_inline)) {
     constexpr bool kInRange = decltype(in_range_tag)::value;
-    constexpr bool kFast = decltype(fast_tag)::value;
-    uint32_t special = 0;
-    [[maybe_unused]] PrepOf<G, CD + 1> prep;
-    if constexpr (G::kHasPrep && !kExp)  // the tick's rotation chain and thrust first (games.hpp)
-      G::template prepare<kInRange, CD + 1>(w, dec, prep, &p.counters[1]);
+    if constexpr (kDecWin)  // the tick's rotation chain and thrust first (games.hpp)
+      G::template prepare<kInRange, CD + 1>(w, dec, pr, &p.counters[1]);
 #pragma unroll
     for (int k = 0; k <= CD; ++k) {
       const int f = f0 + k;
@@ -703,48 +733,31 @@ steady_kernel(const RunParams p) {
       }
       if (dbg & 1u)
         w[0] += win[k];
-      else if constexpr (kFast && !kExp)
-        advance_fast<G>(w, prep, k, special);  // AdvanceFrame{inputs}
       else if constexpr (G::kHasPrep && !kExp) {
 #if RB_WAVE_CLOCK
         {  // (wave clocks: frames in which some lane of the wave takes the speed clamp)
-          const float vx = __uint_as_float(w[2]) * G::kFriction + prep.tx[0][k], vy = __uint_as_float(w[3]) * G::kFriction + prep.ty[0][k];
+          const float vx = __uint_as_float(w[2]) * G::kFriction + pr.tx[0][k], vy = __uint_as_float(w[3]) * G::kFriction + pr.ty[0][k];
           wc_clamp += __any(vx * vx + vy * vy > 49.0f) ? 1u : 0u;
         }
 #endif
-        G::advance_prepared(w, prep, k);  // AdvanceFrame{inputs}
+        G::advance_prepared(w, pr, k);  // AdvanceFrame{inputs}
       }
       else
         G::template advance<kInRange>(w, (dbg & 32u) ? static_cast<InRec>(win[k] & static_cast<InRec>(dbg >> 8)) : win[k],
                                       lane, 0u, &p.counters[1]);  // AdvanceFrame{inputs}
     }
-    return special;
     };
-    if (G::kHasRangePath && __all(G::in_range(w))) {
-      if constexpr (HasFast<G>::value && RB_STEADY_FAST && !kExp) {
-        // Optimistic: every lane of the wave runs the branch-free tick; if any lane met an
-        // operand its division sequence does not cover, the wave runs the tick again from the
-        // loaded state in the general form.  The redo re-executes every request of the tick:
-        // it stores the same cells, checksums and first-seen record over the first pass's (same
-        // lanes, same addresses, program order), re-decides the mismatch and reloads the next
-        // tick's cell.
-        uint32_t w0[NW];
-#pragma unroll
-        for (int i = 0; i < NW; ++i) w0[i] = w[i];
-        if (__any(steps(std::true_type{}, std::true_type{}) != 0u)) {
-#pragma unroll
-          for (int i = 0; i < NW; ++i) w[i] = w0[i];
-          mismatch = kNullFrame;
-          steps(std::false_type{}, std::false_type{});
-        }
-      } else {
-        steps(std::true_type{}, std::false_type{});
-      }
+    if constexpr (kCarry) {
+      steps(std::true_type{}, prep);
+    } else if (G::kHasRangePath && __all(G::in_range(w))) {
+      PrepOf<G, CD + 1> tick_prep;
+      steps(std::true_type{}, tick_prep);
     } else {
 #if RB_WAVE_CLOCK
       ++wc_general;
 #endif
-      steps(std::false_type{}, std::false_type{});
+      PrepOf<G, CD + 1> tick_prep;
+      steps(std::false_type{}, tick_prep);
     }
     if constexpr (G::kDisplay) {
       // Game::last_checksum after the final AdvanceFrame (frame c+1) and the periodic checksum
@@ -782,10 +795,12 @@ steady_kernel(const RunParams p) {
 #pragma unroll
     for (int i = 0; i < NW; ++i) settle(wn[i]);
     // ---- slide the windows to the next tick (c+1): f0 -> f0+1
+    if constexpr (!kCarry) {
 #pragma unroll
-    for (int k = 0; k < CD; ++k) win[k] = win[k + 1];
+      for (int k = 0; k < CD; ++k) win[k] = win[k + 1];
+    }
     win[CD] = next_last;
-    if constexpr (G::kHasPrep) {
+    if constexpr (kDecWin) {
 #pragma unroll
       for (int k = 0; k < CD; ++k) dec[k] = dec[k + 1];
       dec[CD] = G::decode(next_last, lane);
@@ -986,6 +1001,9 @@ struct GameOpsT final : GameOps {
       }
     }
 #endif
+    if constexpr (HasCarry<G, CD>::value) {
+      if (p.T == 1) return rb_launch(steady_kernel<G, CD, false, false>, dim3(grid), dim3(block), p.lds_pad, st, ev, p);
+    }
     return rb_launch(steady_kernel<G, CD, false>, dim3(grid), dim3(block), p.lds_pad, st, ev, p);
   }
   hipError_t launch_steady(const RunParams& p, int cd, int block, hipStream_t st, const LaunchEv& ev) const override {
