@@ -157,6 +157,7 @@ SIGNATURES = [
     ("rb_p2p_run_ticks_packets", _I32, [_P, _I32, _P, ctypes.c_int64, _P, ctypes.c_int64, _P, _P, _P, _P]),
     ("rb_p2p_read_status", _I32, [_P, _P, _P, _P, _P]),
     ("rb_p2p_disconnect_player", _I32, [_P, _I32, _P]),
+    ("rb_p2p_restart_sessions", _I32, [_P, _P]),
     ("rb_p2p_read_frames", _I32, [_P, _P, _P]),
     ("rb_p2p_read_queues", _I32, [_P, _P]),
     ("rb_p2p_read_cells", _I32, [_P, _P, _P, _P]),
@@ -193,6 +194,7 @@ SIGNATURES = [
     ("rb_spectator_set_stream", _I32, [_P, _P]),
     ("rb_spectator_get_stream", _P, [_P]),
     ("rb_spectator_receive_host_status", _I32, [_P, _P, _P]),
+    ("rb_spectator_restart_sessions", _I32, [_P, _P]),
     ("rb_spectator_run_ticks", _I32, [_P, _I32, _P, _P, _I32]),
     ("rb_spectator_read_status", _I32, [_P, _P, _P]),
     ("rb_spectator_read_frames", _I32, [_P, _P, _P]),

@@ -8,6 +8,8 @@
 
 #include "kernels.hpp"
 #include "pacing.hpp"
+#define RB_RESTART_DEFINE  // restart_kernel lives in this translation unit
+#include "restart.hpp"
 #include "time_sync.hpp"
 
 using namespace rb;
@@ -39,6 +41,9 @@ struct rb_p2p {
   int32_t* spec_meta = nullptr;
   std::vector<uint8_t> disconnected;  // host mirror [P][S] of ConnectionStatus::disconnected (validation)
   uint8_t* disc_mask = nullptr;       // [S] device copy of rb_p2p_disconnect_player's session mask
+  uint32_t* tmpl = nullptr;           // the fresh columns restart_kernel copies (restart.hpp PlaneSet::tmpl), from create
+  std::vector<uint32_t> tmpl_host;
+  RestartIndex restart_idx;           // rb_p2p_restart_sessions' selected sessions
   DesyncParams ds{};                  // desync detection buffers (desync_interval > 0)
   PeerParams peer{};                  // peers' connect-status reports (RB_P2P_FLAG_PEER_STATUS)
   int32_t* exp_state = nullptr;       // [2][Spad]: next_spectator_frame, export status (rb_p2p_export_confirmed_inputs)
@@ -91,7 +96,7 @@ void free_all(rb_p2p* b) {
   if (b->stream) (void)hipStreamSynchronize(b->stream);
   void* ptrs[] = {b->snap,   b->cs,      b->tag,       b->ring,       b->live,    b->qs,       b->status,
                   b->trace,  b->counters, b->stats, b->spec_state, b->spec_cells, b->spec_cs, b->spec_meta,
-                  b->disc_mask};
+                  b->disc_mask, b->tmpl};
   for (void* q : ptrs)
     if (q) (void)hipFree(q);
   void* dptrs[] = {b->ds.lh_frame, b->ds.lh_cs,    b->ds.rh_frame, b->ds.rh_lo,     b->ds.rh_hi,
@@ -99,6 +104,7 @@ void free_all(rb_p2p* b) {
                    b->ds.ev_frame, b->ds.ev_handle, b->ds.ev_local, b->ds.ev_remote};
   for (void* q : dptrs)
     if (q) (void)hipFree(q);
+  b->restart_idx.release();
   if (b->fan.dev) (void)hipFree(b->fan.dev);
   if (b->fan.host) (void)hipHostFree(b->fan.host);
   if (b->fan.ev) (void)hipEventDestroy(b->fan.ev);
@@ -285,16 +291,104 @@ void image_from_planes(const rb_p2p* b, const std::vector<uint32_t>& planes, int
 }  // namespace
 
 namespace {
-// The pacing buffers, made by the first call that needs them: nothing parked yet, acc = 0.
+// ---- What a fresh session holds, one function per buffer group (restart.hpp).  The call that makes
+// a group's buffers writes these values into every column, rb_p2p_restart_sessions into the selected
+// sessions' columns: the values stand here and nowhere else.  A group whose buffers do not exist
+// adds nothing.  Batch-wide buffers (counters, stats, the fan-out's sums) are not per session.
+
+// SyncLayer::new, InputQueue::new and ConnectionStatus::default for every handle, no tick yet
+void core_planes(const rb_p2p* b, PlaneSet& ps) {
+  const int NW = b->ops->nw, L = b->ops->lanes;
+  std::vector<uint32_t> w0(static_cast<size_t>(L) * NW);
+  b->ops->init_words(w0.data());
+  ps.state(b->live, NW, L, 1, w0.data());  // State::new
+  ps.state(b->snap, NW, L, b->W, nullptr);
+  ps.fill(b->cs, b->ops->cs_bytes, b->W, 1, 0);
+  ps.fill(b->tag, 4, b->W, 1, 0xff);  // GameState::default frame = NULL_FRAME
+  ps.fill(b->ring, b->ops->input_bytes, static_cast<size_t>(kQueueLen) * b->P, 1, 0);  // blank inputs
+  ps.fill(b->status, 4, 1, 1, 0);
+  ps.fill(b->trace, 4, 1, 1, 0xff);  // no tick yet: NULL load frame (at frame 0), counts 0xFF
+  // every frame NULL, current 0, connected, length 0, the first input at frame 0 (q_pack)
+  std::vector<int32_t> qs(kQsFields, kNullFrame);
+  const QPacked q0 = q_pack(QFields{kNullFrame, kNullFrame, kNullFrame, kNullFrame, kNullFrame, 0, 0, false, 0u}, 0);
+  qs[QS_CUR] = 0;
+  qs[QS_SAVED_CONF] = static_cast<int32_t>(fd_enc(kNullFrame, 0) | fd_enc(kNullFrame, 0) << 16);
+  for (int h = 0; h < 4; ++h) {
+    for (int i = 0; i < 4; ++i) qs[QS_PLAYER0 + (QF_LA_CONN + i) * 4 + h] = static_cast<int32_t>(q0.w[i]);
+    qs[QS_PLAYER0 + QF_PRED_VAL * 4 + h] = 0;
+    qs[QS_PLAYER0 + QF_MTF_N * 4 + h] = 0;  // the fan-out's candidate list starts empty
+  }
+  ps.row_values(b->qs, 1, qs);
+}
+// the fan-out: nothing valid yet.  The branch planes are read only behind a valid row.
+void fanout_planes(const rb_p2p* b, PlaneSet& ps) {
+  if (b->spec_meta) ps.fill(b->spec_meta, 4, SM_COUNT, 1, 0);
+}
+// ConnectionStatus::default for every (endpoint, player)
+void peer_planes(const rb_p2p* b, PlaneSet& ps) {
+  if (!b->peer.last) return;
+  ps.fill(b->peer.last, 4, 16, 1, 0xff);  // NULL_FRAME
+  ps.fill(b->peer.disc, 4, 16, 1, 0);
+}
+// empty histories, outbox and event rings (entries behind a count or a NULL frame are never read)
+void desync_planes(const rb_p2p* b, PlaneSet& ps) {
+  const DesyncParams& d = b->ds;
+  if (!d.lh_frame) return;
+  ps.fill(d.lh_frame, 4, kCsHist, 1, 0xff);  // NULL_FRAME: empty slot
+  ps.fill(d.lh_cs, 8, kCsHist, 1, 0);
+  ps.fill(d.rh_frame, 4, 4 * kCsHist, 1, 0xff);
+  ps.row_values(d.rh_meta, 4, {0, 0, kNullFrame});  // head 0, length 0, last_added_checksum_frame NULL_FRAME
+  ps.fill(d.ob_n, 4, 1, 1, 0);
+  ps.fill(d.ev_n, 4, 1, 1, 0);
+  ps.fill(d.ev_frame, 4, kEvents, 1, 0xff);
+  ps.fill(d.ev_handle, 4, kEvents, 1, 0xff);
+}
+// next_spectator_frame = 0 (p2p_session.rs:201), status RB_P2P_EXPORT_OK
+void export_planes(const rb_p2p* b, PlaneSet& ps) {
+  if (b->exp_state) ps.fill(b->exp_state, 4, 2, 1, 0);
+}
+// TimeSync::default, local / remote_frame_advantage 0, round_trip_time 0, next_recommended_sleep 0,
+// frames_ahead 0, no event
+void time_sync_planes(const rb_p2p* b, PlaneSet& ps) {
+  if (!b->ts.state) return;
+  ps.fill(b->ts.state, 4, TS_ROWS, 1, 0);
+  ps.fill(b->ts.win, 4, 2 * static_cast<size_t>(kTsWindow) * 4, 1, 0);
+}
+// nothing parked yet, acc = 0
+void pace_planes(const rb_p2p* b, PlaneSet& ps) {
+  if (!b->pace.view) return;
+  ps.fill(b->pace.view, 4, 1, 1, 0);
+  ps.fill(b->pace.parked, 4, 1, 1, 0);
+  ps.fill(b->pace.acc, 4, 1, 1, 0);
+}
+// every group the batch has, the groups with templates first (their offsets are those of create)
+void all_planes(const rb_p2p* b, PlaneSet& ps) {
+  ps.Spad = static_cast<size_t>(b->Spad);
+  core_planes(b, ps);
+  desync_planes(b, ps);
+  fanout_planes(b, ps);
+  peer_planes(b, ps);
+  export_planes(b, ps);
+  time_sync_planes(b, ps);
+  pace_planes(b, ps);
+}
+// a freshly made group's values into every column, padding included
+hipError_t fill_group(const rb_p2p* b, void (*group)(const rb_p2p*, PlaneSet&)) {
+  PlaneSet ps;
+  ps.Spad = static_cast<size_t>(b->Spad);
+  group(b, ps);
+  ps.bind(b->tmpl);
+  return restart_launch(ps, nullptr, static_cast<uint32_t>(b->Spad), b->stream);
+}
+
+// The pacing buffers, made by the first call that needs them.
 rb_status pace_reserve(rb_p2p* b) {
   if (b->pace.view) return RB_OK;
   const size_t bytes = static_cast<size_t>(b->Spad) * 4;
   P2P_TRY(b, hipMalloc(&b->pace.view, bytes));
   P2P_TRY(b, hipMalloc(&b->pace.parked, bytes));
   P2P_TRY(b, hipMalloc(&b->pace.acc, bytes));
-  P2P_TRY(b, hipMemsetAsync(b->pace.view, 0, bytes, b->stream));
-  P2P_TRY(b, hipMemsetAsync(b->pace.parked, 0, bytes, b->stream));
-  P2P_TRY(b, hipMemsetAsync(b->pace.acc, 0, bytes, b->stream));
+  P2P_TRY(b, fill_group(b, pace_planes));
   return RB_OK;
 }
 template <int IB>
@@ -410,12 +504,7 @@ rb_status rb_p2p_create(const rb_p2p_config* cfg, rb_p2p** out) {
   P2P_CREATE(hipMalloc(&b->trace, Sp * 4));
   P2P_CREATE(hipMalloc(&b->counters, 16));
   P2P_CREATE(hipMalloc(&b->stats, ST_COUNT * Sp * 8));
-  P2P_CREATE(hipMemsetAsync(b->snap, 0, W * NW * Gp * 4, b->stream));
-  P2P_CREATE(hipMemsetAsync(b->cs, 0, W * Sp * b->ops->cs_bytes, b->stream));
-  P2P_CREATE(hipMemsetAsync(b->tag, 0xff, W * Sp * 4, b->stream));  // GameState::default frame = NULL_FRAME
-  P2P_CREATE(hipMemsetAsync(b->ring, 0, ring_bytes, b->stream));     // blank inputs
-  P2P_CREATE(hipMemsetAsync(b->status, 0, Sp * 4, b->stream));
-  P2P_CREATE(hipMemsetAsync(b->trace, 0xff, Sp * 4, b->stream));  // no tick yet: NULL load frame (at frame 0), counts 0xFF
+  // the per-session buffers are filled below, from the plane groups
   P2P_CREATE(hipMemsetAsync(b->counters, 0, 16, b->stream));
   P2P_CREATE(hipMemsetAsync(b->stats, 0, ST_COUNT * Sp * 8, b->stream));
   if (b->fanout) {
@@ -426,7 +515,6 @@ rb_status rb_p2p_create(const rb_p2p_config* cfg, rb_p2p** out) {
     P2P_CREATE(hipMalloc(&b->spec_cells, W * K * NW * Gp * 4));
     P2P_CREATE(hipMalloc(&b->spec_cs, W * K * Sp * b->ops->cs_bytes));
     P2P_CREATE(hipMalloc(&b->spec_meta, SM_COUNT * Sp * 4));
-    P2P_CREATE(hipMemsetAsync(b->spec_meta, 0, SM_COUNT * Sp * 4, b->stream));  // nothing valid yet
     b->fan.adaptive = (cfg->flags & RB_P2P_FLAG_FANOUT_ALWAYS) == 0;
     if (cfg->fanout_min_select_permille) b->fan.min_permille = cfg->fanout_min_select_permille;
     if (b->fan.adaptive) {
@@ -435,30 +523,14 @@ rb_status rb_p2p_create(const rb_p2p_config* cfg, rb_p2p** out) {
       P2P_CREATE(hipEventCreateWithFlags(&b->fan.ev, hipEventDisableTiming));
     }
   }
-  // SyncLayer::new / InputQueue::new / ConnectionStatus::default: every frame NULL, current 0,
-  // connected, length 0, the first input at frame 0 (q_pack)
-  std::vector<int32_t> qs(kQsFields * Sp, kNullFrame);
-  const QPacked q0 = q_pack(QFields{kNullFrame, kNullFrame, kNullFrame, kNullFrame, kNullFrame, 0, 0, false, 0u}, 0);
-  for (size_t s = 0; s < Sp; ++s) {
-    qs[QS_CUR * Sp + s] = 0;
-    qs[QS_SAVED_CONF * Sp + s] = static_cast<int32_t>(fd_enc(kNullFrame, 0) | fd_enc(kNullFrame, 0) << 16);
-    for (int h = 0; h < 4; ++h) {
-      for (int i = 0; i < 4; ++i) qs[(QS_PLAYER0 + (QF_LA_CONN + i) * 4 + h) * Sp + s] = static_cast<int32_t>(q0.w[i]);
-      qs[(QS_PLAYER0 + QF_PRED_VAL * 4 + h) * Sp + s] = 0;
-      qs[(QS_PLAYER0 + QF_MTF_N * 4 + h) * Sp + s] = 0;  // the fan-out's candidate list starts empty
-    }
-  }
   b->disconnected.assign(static_cast<size_t>(b->P) * b->S, 0);
   P2P_CREATE(hipMalloc(&b->disc_mask, Sp));
-  P2P_CREATE(hipMemcpyAsync(b->qs, qs.data(), qs.size() * 4, hipMemcpyHostToDevice, b->stream));
-  if (cfg->flags & RB_P2P_FLAG_PEER_STATUS) {  // ConnectionStatus::default for every (endpoint, player)
+  if (cfg->flags & RB_P2P_FLAG_PEER_STATUS) {
     P2P_CREATE(hipMalloc(&b->peer.last, 16 * Sp * 4));
     P2P_CREATE(hipMalloc(&b->peer.disc, 16 * Sp * 4));
-    P2P_CREATE(hipMemsetAsync(b->peer.last, 0xff, 16 * Sp * 4, b->stream));  // NULL_FRAME
-    P2P_CREATE(hipMemsetAsync(b->peer.disc, 0, 16 * Sp * 4, b->stream));
     b->peer.on = 1;
   }
-  if (cfg->desync_interval > 0) {  // empty histories, outbox and event rings
+  if (cfg->desync_interval > 0) {
     DesyncParams& d = b->ds;
     d.interval = cfg->desync_interval;
     const size_t H = kCsHist, R = 4;
@@ -476,27 +548,16 @@ rb_status rb_p2p_create(const rb_p2p_config* cfg, rb_p2p** out) {
     P2P_CREATE(hipMalloc(&d.ev_handle, kEvents * Sp * 4));
     P2P_CREATE(hipMalloc(&d.ev_local, kEvents * Sp * 8));
     P2P_CREATE(hipMalloc(&d.ev_remote, kEvents * Sp * 8));
-    P2P_CREATE(hipMemsetAsync(d.lh_frame, 0xff, H * Sp * 4, b->stream));  // NULL_FRAME: empty slot
-    P2P_CREATE(hipMemsetAsync(d.lh_cs, 0, H * Sp * 8, b->stream));
-    P2P_CREATE(hipMemsetAsync(d.rh_frame, 0xff, R * H * Sp * 4, b->stream));
-    std::vector<int32_t> meta(R * 3 * Sp, 0);  // head 0, length 0, last_added_checksum_frame NULL_FRAME
-    for (size_t h = 0; h < R; ++h)
-      for (size_t s = 0; s < Sp; ++s) meta[(h * 3 + 2) * Sp + s] = kNullFrame;
-    P2P_CREATE(hipMemcpy(d.rh_meta, meta.data(), meta.size() * 4, hipMemcpyHostToDevice));
-    P2P_CREATE(hipMemsetAsync(d.ob_n, 0, Sp * 4, b->stream));
-    P2P_CREATE(hipMemsetAsync(d.ev_n, 0, Sp * 4, b->stream));
-    P2P_CREATE(hipMemsetAsync(d.ev_frame, 0xff, kEvents * Sp * 4, b->stream));
-    P2P_CREATE(hipMemsetAsync(d.ev_handle, 0xff, kEvents * Sp * 4, b->stream));
   }
-  // State::new for every session
-  std::vector<uint32_t> w0(L * NW), planes(NW * Gp);
-  b->ops->init_words(w0.data());
-  for (size_t s = 0; s < Sp; ++s)
-    for (size_t l = 0; l < L; ++l)
-      for (size_t k = 0; k < NW; ++k)
-        planes[word_index(static_cast<int>(NW), static_cast<int>(Gp), static_cast<int>(s * L + l), static_cast<int>(k))] =
-            w0[l * NW + k];
-  P2P_CREATE(hipMemcpyAsync(b->live, planes.data(), planes.size() * 4, hipMemcpyHostToDevice, b->stream));
+  // every session fresh: the plane groups' values into every column, their templates kept on the
+  // device for rb_p2p_restart_sessions
+  PlaneSet ps;
+  all_planes(bp, ps);
+  b->tmpl_host = ps.tmpl;
+  P2P_CREATE(hipMalloc(&b->tmpl, ps.tmpl.size() * 4));
+  P2P_CREATE(hipMemcpyAsync(b->tmpl, ps.tmpl.data(), ps.tmpl.size() * 4, hipMemcpyHostToDevice, b->stream));
+  ps.bind(b->tmpl);
+  P2P_CREATE(restart_launch(ps, nullptr, static_cast<uint32_t>(b->Spad), b->stream));
   P2P_CREATE(hipStreamSynchronize(b->stream));
 #undef P2P_CREATE
   *out = b.release();
@@ -947,6 +1008,29 @@ rb_status rb_p2p_disconnect_player(rb_p2p* b, int32_t handle, const uint8_t* ses
   return RB_OK;
 }
 
+rb_status rb_p2p_restart_sessions(rb_p2p* b, const uint8_t* session_mask) {
+  std::vector<int32_t> idx;
+  if (session_mask) {
+    restart_selected(session_mask, b->S, idx);
+    if (idx.empty()) return RB_OK;
+  }
+  const bool all = !session_mask || idx.size() == static_cast<size_t>(b->S);
+  DeviceScope dev_scope(b->device);
+  PlaneSet ps;
+  all_planes(b, ps);
+  if (ps.tmpl != b->tmpl_host) return pfail(b, RB_DEVICE_ERROR, "rb_p2p_restart_sessions: the templates moved since create");
+  ps.bind(b->tmpl);
+  if (!all) P2P_TRY(b, b->restart_idx.upload(idx, static_cast<size_t>(b->S), b->stream));
+  P2P_TRY(b, restart_launch(ps, all ? nullptr : b->restart_idx.dev, all ? static_cast<uint32_t>(b->S) : static_cast<uint32_t>(idx.size()),
+                            b->stream));
+  // the host mirror of ConnectionStatus::disconnected
+  if (all) std::fill(b->disconnected.begin(), b->disconnected.end(), uint8_t{0});
+  else
+    for (int h = 0; h < b->P; ++h)
+      for (int32_t s : idx) b->disconnected[static_cast<size_t>(h) * b->S + s] = 0;
+  return RB_OK;
+}
+
 rb_status rb_p2p_read_status(rb_p2p* b, int32_t* status, int32_t* load_frame, int32_t* n_adv, int32_t* n_save) {
   std::vector<int32_t> st, tr, cur;
   rb_status r = read_rows(b, b->status, 1, st);
@@ -1097,9 +1181,9 @@ rb_status rb_p2p_export_confirmed_inputs(rb_p2p* b, void* inputs_by_frame, int32
   if (!inputs_by_frame || !upto || !last_frames || !disconnected || frames <= 0)
     return pfail(b, RB_INVALID_REQUEST, "rb_p2p_export_confirmed_inputs: missing output tensor");
   DeviceScope dev_scope(b->device);
-  if (!b->exp_state) {  // next_spectator_frame = 0 (p2p_session.rs:201), status OK
+  if (!b->exp_state) {
     P2P_TRY(b, hipMalloc(&b->exp_state, 2 * static_cast<size_t>(b->Spad) * 4));
-    P2P_TRY(b, hipMemsetAsync(b->exp_state, 0, 2 * static_cast<size_t>(b->Spad) * 4, b->stream));
+    P2P_TRY(b, fill_group(b, export_planes));
   }
   const dim3 grid((b->S + 255) / 256), block(256);
   auto k = b->ops->input_bytes == 4 ? p2p_export_kernel<4> : p2p_export_kernel<1>;
@@ -1147,10 +1231,7 @@ rb_status rb_p2p_time_sync_enable(rb_p2p* b, int32_t fps) {
   b->ts.state = state;
   b->ts.win = win;
   b->ts.fps = fps;
-  // TimeSync::default, local / remote_frame_advantage 0, round_trip_time 0, next_recommended_sleep 0,
-  // frames_ahead 0, no event
-  P2P_TRY(b, hipMemsetAsync(state, 0, st, b->stream));
-  P2P_TRY(b, hipMemsetAsync(win, 0, wn, b->stream));
+  P2P_TRY(b, fill_group(b, time_sync_planes));
   b->ts_on = true;
   return RB_OK;
 }

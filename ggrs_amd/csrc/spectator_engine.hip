@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "kernels.hpp"
+#include "restart.hpp"
 
 using namespace rb;
 
@@ -22,6 +23,8 @@ struct rb_spectator {
   int32_t* host = nullptr;    // [2][4][Spad] host_connect_status: last_frame, disconnected
   unsigned long long* stats = nullptr;  // [SPT_COUNT][Spad]
   uint32_t* counters = nullptr;         // [1] unexpected math paths
+  uint32_t* tmpl = nullptr;             // the fresh columns restart_kernel copies (restart.hpp PlaneSet::tmpl)
+  RestartIndex restart_idx;             // rb_spectator_restart_sessions' selected sessions
   std::string last_err;
 };
 
@@ -54,9 +57,10 @@ struct DeviceScope {
 void free_all(rb_spectator* b) {
   (void)hipSetDevice(b->device);
   if (b->stream) (void)hipStreamSynchronize(b->stream);
-  void* ptrs[] = {b->live, b->cs, b->frames, b->status, b->host, b->stats, b->counters};
+  void* ptrs[] = {b->live, b->cs, b->frames, b->status, b->host, b->stats, b->counters, b->tmpl};
   for (void* q : ptrs)
     if (q) (void)hipFree(q);
+  b->restart_idx.release();
   if (b->own_stream) (void)hipStreamDestroy(b->own_stream);
 }
 
@@ -78,6 +82,22 @@ __global__ void spectator_host_status_kernel(int32_t* __restrict__ host, const i
     host[o] = max(host[o], last[static_cast<size_t>(i) * S + s]);
     host[d] = host[d] | (disc[static_cast<size_t>(i) * S + s] ? 1 : 0);
   }
+}
+
+// What a fresh spectator holds (restart.hpp): written into every column by rb_spectator_create and
+// into the selected sessions' columns by rb_spectator_restart_sessions.  stats and counters are
+// batch-wide.
+void spectator_planes(const rb_spectator* b, PlaneSet& ps) {
+  ps.Spad = static_cast<size_t>(b->Spad);
+  const int NW = b->ops->nw, L = b->ops->lanes;
+  std::vector<uint32_t> w0(static_cast<size_t>(L) * NW);
+  b->ops->init_words(w0.data());
+  ps.state(b->live, NW, L, 1, w0.data());  // State::new
+  ps.fill(b->cs, b->ops->cs_bytes, 1, 1, 0);
+  ps.fill(b->frames, 4, 2, 1, 0xff);        // current_frame, last_recv_frame: NULL_FRAME (:67-68)
+  ps.row_values(b->status, 1, {0, -1});     // RB_OK; no tick yet
+  ps.fill(b->host, 4, 4, 1, 0xff);          // ConnectionStatus::default: last_frame NULL_FRAME
+  ps.fill(b->host + 4 * ps.Spad, 4, 4, 1, 0);  // connected
 }
 }  // namespace
 
@@ -157,23 +177,15 @@ rb_status rb_spectator_create(const rb_spectator_config* cfg, rb_spectator** out
   SPT_CREATE(hipMalloc(&b->host, 8 * Sp * 4));
   SPT_CREATE(hipMalloc(&b->stats, SPT_COUNT * Sp * 8));
   SPT_CREATE(hipMalloc(&b->counters, 16));
-  SPT_CREATE(hipMemsetAsync(b->cs, 0, Sp * b->ops->cs_bytes, b->stream));
-  SPT_CREATE(hipMemsetAsync(b->frames, 0xff, 2 * Sp * 4, b->stream));  // current_frame, last_recv_frame: NULL_FRAME (:67-68)
-  SPT_CREATE(hipMemsetAsync(b->status, 0, Sp * 4, b->stream));
-  SPT_CREATE(hipMemsetAsync(b->status + Sp, 0xff, Sp * 4, b->stream));  // no tick yet
-  SPT_CREATE(hipMemsetAsync(b->host, 0xff, 4 * Sp * 4, b->stream));     // ConnectionStatus::default: last_frame NULL_FRAME
-  SPT_CREATE(hipMemsetAsync(b->host + 4 * Sp, 0, 4 * Sp * 4, b->stream));  // connected
   SPT_CREATE(hipMemsetAsync(b->stats, 0, SPT_COUNT * Sp * 8, b->stream));
   SPT_CREATE(hipMemsetAsync(b->counters, 0, 16, b->stream));
-  // State::new for every session
-  std::vector<uint32_t> w0(L * NW), planes(NW * Gp);
-  b->ops->init_words(w0.data());
-  for (size_t s = 0; s < Sp; ++s)
-    for (size_t l = 0; l < L; ++l)
-      for (size_t k = 0; k < NW; ++k)
-        planes[word_index(static_cast<int>(NW), static_cast<int>(Gp), static_cast<int>(s * L + l), static_cast<int>(k))] =
-            w0[l * NW + k];
-  SPT_CREATE(hipMemcpyAsync(b->live, planes.data(), planes.size() * 4, hipMemcpyHostToDevice, b->stream));
+  // every session fresh: spectator_planes' values into every column, padding included
+  PlaneSet ps;
+  spectator_planes(bp, ps);
+  SPT_CREATE(hipMalloc(&b->tmpl, ps.tmpl.size() * 4));
+  SPT_CREATE(hipMemcpyAsync(b->tmpl, ps.tmpl.data(), ps.tmpl.size() * 4, hipMemcpyHostToDevice, b->stream));
+  ps.bind(b->tmpl);
+  SPT_CREATE(restart_launch(ps, nullptr, static_cast<uint32_t>(b->Spad), b->stream));
   SPT_CREATE(hipStreamSynchronize(b->stream));
 #undef SPT_CREATE
   *out = b.release();
@@ -203,6 +215,23 @@ rb_status rb_spectator_receive_host_status(rb_spectator* b, const int32_t* last_
   hipLaunchKernelGGL(spectator_host_status_kernel, dim3((b->S + 255) / 256), dim3(256), 0, b->stream, b->host,
                      last_frames, disconnected, b->S, b->Spad, b->P);
   SPT_TRY(b, hipGetLastError());
+  return RB_OK;
+}
+
+rb_status rb_spectator_restart_sessions(rb_spectator* b, const uint8_t* session_mask) {
+  std::vector<int32_t> idx;
+  if (session_mask) {
+    restart_selected(session_mask, b->S, idx);
+    if (idx.empty()) return RB_OK;
+  }
+  const bool all = !session_mask || idx.size() == static_cast<size_t>(b->S);
+  DeviceScope dev_scope(b->device);
+  PlaneSet ps;
+  spectator_planes(b, ps);  // the same function, so the same template offsets, as at create
+  ps.bind(b->tmpl);
+  if (!all) SPT_TRY(b, b->restart_idx.upload(idx, static_cast<size_t>(b->S), b->stream));
+  SPT_TRY(b, restart_launch(ps, all ? nullptr : b->restart_idx.dev, all ? static_cast<uint32_t>(b->S) : static_cast<uint32_t>(idx.size()),
+                            b->stream));
   return RB_OK;
 }
 

@@ -186,6 +186,21 @@ class P2PSession(_StreamOrdered):
             raise InvalidRequest((self._lib.rb_p2p_last_error(self._h) or b"").decode())
         self._check(st)
 
+    def restart_sessions(self, sessions=None) -> None:
+        """Drop the P2PSession and start_p2p_session again (builder.rs:251-308) in every session
+        where `sessions` is true (None: all), between ticks (rb_p2p_restart_sessions): the
+        session is what a freshly created batch holds, its next tick is its frame 0 and its
+        deliveries, packets and export rows count from 0 again.  The other sessions are untouched;
+        counters() and totals() continue since create.  Read a session's desync events, wait
+        recommendations or parked ticks before restarting it."""
+        m = None
+        if sessions is not None:
+            m = np.ascontiguousarray(np.broadcast_to(np.asarray(sessions), (self.num_sessions,)), dtype=np.uint8)
+        st = self._lib.rb_p2p_restart_sessions(self._h, None if m is None else m.ctypes.data_as(ctypes.c_void_p))
+        if st == L.RB_INVALID_REQUEST:
+            raise InvalidRequest((self._lib.rb_p2p_last_error(self._h) or b"").decode())
+        self._check(st)
+
     def advance_frame(self, local_inputs, remote_upto, remote_inputs, run=None) -> None:
         """One tick (run_ticks with T = 1): local_inputs [P, S], remote_upto [P, S];
         run None, or [S] uint8: 0 parks the session for this tick."""

@@ -89,6 +89,16 @@ class SpectatorSession(_StreamOrdered):
         self._post(cur, (lk, dk))
         self._check(st)
 
+    def restart_sessions(self, sessions=None) -> None:
+        """start_spectator_session again in every session where `sessions` is true (None: all),
+        between ticks (rb_spectator_restart_sessions): the spectator follows its host's next
+        match from frame 0.  The other sessions are untouched; totals() continues since create."""
+        m = None
+        if sessions is not None:
+            m = np.ascontiguousarray(np.broadcast_to(np.asarray(sessions), (self.num_sessions,)), dtype=np.uint8)
+        st = self._lib.rb_spectator_restart_sessions(self._h, None if m is None else m.ctypes.data_as(ctypes.c_void_p))
+        self._check(st)
+
     def run_ticks(self, host_upto, host_inputs) -> None:
         """T ticks of advance_frame + handle_requests in one device launch.
 

@@ -417,6 +417,29 @@ rb_status rb_p2p_run_ticks_packets(rb_p2p* b, int32_t n_ticks, const void* local
  * resimulates from last_frame + 1 if that frame was already simulated. */
 rb_status rb_p2p_disconnect_player(rb_p2p* b, int32_t handle, const uint8_t* session_mask);
 
+/* Dropping the P2PSession and calling SessionBuilder::start_p2p_session
+ * (builder.rs:251-308) again with the same builder, in every session whose
+ * `session_mask` byte is non-zero (host pointer, [S] bytes; NULL: all
+ * sessions), called between rb_p2p_run_ticks calls: stream ordered, without a
+ * host synchronisation (the mask is consumed before the call returns); an empty
+ * selection launches nothing.  Every per-session value of a selected session
+ * becomes what rb_p2p_create writes (and rb_p2p_time_sync_enable, the first
+ * export and the first paced tick, where the batch has used them): the live
+ * state, all cells, the input ring, the bookkeeping rows with their escape and
+ * move-to-front rows, the status and trace words (a panicked session runs
+ * again), the desync histories, outbox and event ring, the peers'
+ * connect-status rows, the export's next_spectator_frame and status
+ * (RB_P2P_EXPORT_OVERRUN is cleared), the time-sync rows, windows and
+ * WaitRecommendation ring, the pacing view, parked-tick count and accumulator,
+ * and the fan-out's branch validity.  A caller that wants a session's events,
+ * recommendations or parked count reads them first.  The session's next tick
+ * is its frame 0: its deliveries, packets' start frames and export rows count
+ * from 0 again.  Unselected sessions are untouched.  Batch-wide values continue
+ * since create: rb_p2p_counters, rb_p2p_totals, the adaptive fan-out's policy,
+ * the launch clock and the profile events; rb_p2p_time_sync_enable stays
+ * closed. */
+rb_status rb_p2p_restart_sessions(rb_p2p* b, const uint8_t* session_mask);
+
 /* Per session, the last tick: rb_status of its advance_frame, the LoadGameState
  * frame (RB_NULL_FRAME: no rollback), AdvanceFrame and SaveGameState counts.
  * Any pointer may be NULL.  Synchronises. */
@@ -712,6 +735,14 @@ void* rb_spectator_get_stream(const rb_spectator* b); /* as rb_get_stream */
  * (stored.disconnected || reported, max(stored.last_frame, reported)).
  * Stream ordered before the next launch. */
 rb_status rb_spectator_receive_host_status(rb_spectator* b, const int32_t* last_frames, const uint8_t* disconnected);
+
+/* start_spectator_session again for every session whose `session_mask` byte
+ * is non-zero (rb_p2p_restart_sessions' convention; NULL: all), between
+ * rb_spectator_run_ticks calls, stream ordered: the state, checksum, frames,
+ * last status and host connect status become what rb_spectator_create writes,
+ * so the spectator follows its host's next match from frame 0.  Unselected
+ * sessions are untouched; rb_spectator_totals continues since create. */
+rb_status rb_spectator_restart_sessions(rb_spectator* b, const uint8_t* session_mask);
 
 /* n_ticks x SpectatorSession::advance_frame (+ handle_requests) for every
  * session, in ONE device launch.  Device pointers, stream ordered:
