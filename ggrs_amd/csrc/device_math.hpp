@@ -6,9 +6,12 @@
 //   (sysdeps/ieee754/flt-32/s_sinf.c, s_cosf.c, sincosf.h, sincosf_data.c:
 //   reduce_fast + degree-4/5 polynomials).  That algorithm is restated here in
 //   double arithmetic, which the GPU executes with IEEE-exact add/mul/fma, so
-//   device results equal glibc's.  Checked exhaustively against the host libm
-//   for every float in [-0.1, 6.4] (tests/test_device_math.py, GPU) and on the
-//   host for all 2.1e9 floats of that range when this file was written.
+//   device results equal glibc's.  Checked against the host libm on the GPU by
+//   tests/test_gpu_parity.py: test_device_sincosf_bit_exact_with_glibc (every
+//   37th float of [-0.1, 6.4] and the special values) and
+//   test_device_inrange_sincos_and_rotation_step_every_float (the in-range form
+//   for every float of [+0, 6.5)); and on the host for all 2.1e9 floats of
+//   [-0.1, 6.4] when this file was written.
 //   Only |x| < 120 is restated (ex_game rotations live in [0, 2*pi]); larger
 //   arguments fall back to the ocml routines and are counted as unexpected.
 // * fletcher16 closed form: the serial mod-255 loop of ex_game.rs:42-52 equals
