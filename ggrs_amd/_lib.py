@@ -158,6 +158,9 @@ SIGNATURES = [
     ("rb_p2p_read_status", _I32, [_P, _P, _P, _P, _P]),
     ("rb_p2p_disconnect_player", _I32, [_P, _I32, _P]),
     ("rb_p2p_restart_sessions", _I32, [_P, _P]),
+    ("rb_p2p_export_sessions", _I32, [_P, _P, _I32, _P]),
+    ("rb_p2p_import_sessions", _I32, [_P, _P, _I32, _P]),
+    ("rb_p2p_import_refused", _I32, [_P, _P]),
     ("rb_p2p_read_frames", _I32, [_P, _P, _P]),
     ("rb_p2p_read_queues", _I32, [_P, _P]),
     ("rb_p2p_read_cells", _I32, [_P, _P, _P, _P]),
@@ -195,6 +198,9 @@ SIGNATURES = [
     ("rb_spectator_get_stream", _P, [_P]),
     ("rb_spectator_receive_host_status", _I32, [_P, _P, _P]),
     ("rb_spectator_restart_sessions", _I32, [_P, _P]),
+    ("rb_spectator_export_sessions", _I32, [_P, _P, _I32, _P]),
+    ("rb_spectator_import_sessions", _I32, [_P, _P, _I32, _P]),
+    ("rb_spectator_import_refused", _I32, [_P, _P]),
     ("rb_spectator_run_ticks", _I32, [_P, _I32, _P, _P, _I32]),
     ("rb_spectator_read_status", _I32, [_P, _P, _P]),
     ("rb_spectator_read_frames", _I32, [_P, _P, _P]),
@@ -206,6 +212,12 @@ SIGNATURES = [
                                         _P, _P]),
     ("rb_encode_input_packets", _I32, [_I32, _P, _I32, _I32, _I32, _I32, _P, _I32, _I32, _P, _P, _P, ctypes.c_int64,
                                         _P, _P]),
+]
+
+# the entry points that return a 64-bit size
+SIZE_SIGNATURES = [
+    ("rb_p2p_session_record_bytes", ctypes.c_int64, [_P]),
+    ("rb_spectator_session_record_bytes", ctypes.c_int64, [_P]),
 ]
 
 _lib = None
@@ -222,7 +234,7 @@ def load() -> ctypes.CDLL:
             "(or __graft_entry__.build()); the engine has no CPU fallback."
         )
     lib = ctypes.CDLL(LIB_PATH)
-    for name, res, args in SIGNATURES:
+    for name, res, args in SIGNATURES + SIZE_SIGNATURES:
         if os.environ.get("GGRS_AMD_LIB") and not hasattr(lib, name):
             continue  # an older experiment build may lack newer entry points
         fn = getattr(lib, name)

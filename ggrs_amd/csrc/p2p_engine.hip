@@ -8,8 +8,8 @@
 
 #include "kernels.hpp"
 #include "pacing.hpp"
-#define RB_RESTART_DEFINE  // restart_kernel lives in this translation unit
-#include "restart.hpp"
+#define RB_RESTART_DEFINE  // restart_kernel and the move kernels live in this translation unit
+#include "migrate.hpp"
 #include "time_sync.hpp"
 
 using namespace rb;
@@ -44,6 +44,9 @@ struct rb_p2p {
   uint32_t* tmpl = nullptr;           // the fresh columns restart_kernel copies (restart.hpp PlaneSet::tmpl), from create
   std::vector<uint32_t> tmpl_host;
   RestartIndex restart_idx;           // rb_p2p_restart_sessions' selected sessions
+  RestartIndex move_idx;              // rb_p2p_export_sessions' / rb_p2p_import_sessions' (a restart in flight keeps its own slots)
+  uint32_t* refused = nullptr;        // [1] records rb_p2p_import_sessions refused since create (made by the first import)
+  bool mirror_stale = false;          // an import wrote qs: `disconnected` is refreshed from it before its next use
   DesyncParams ds{};                  // desync detection buffers (desync_interval > 0)
   PeerParams peer{};                  // peers' connect-status reports (RB_P2P_FLAG_PEER_STATUS)
   int32_t* exp_state = nullptr;       // [2][Spad]: next_spectator_frame, export status (rb_p2p_export_confirmed_inputs)
@@ -105,6 +108,8 @@ void free_all(rb_p2p* b) {
   for (void* q : dptrs)
     if (q) (void)hipFree(q);
   b->restart_idx.release();
+  b->move_idx.release();
+  if (b->refused) (void)hipFree(b->refused);
   if (b->fan.dev) (void)hipFree(b->fan.dev);
   if (b->fan.host) (void)hipHostFree(b->fan.host);
   if (b->fan.ev) (void)hipEventDestroy(b->fan.ev);
@@ -320,9 +325,14 @@ void core_planes(const rb_p2p* b, PlaneSet& ps) {
   }
   ps.row_values(b->qs, 1, qs);
 }
-// the fan-out: nothing valid yet.  The branch planes are read only behind a valid row.
+// the fan-out: nothing valid yet.  The branch planes (spec_state, spec_cells, spec_cs) are read only
+// behind a valid row, and a row is valid only for the tick after the launch that made it, unless
+// the batch's adaptive policy has cleared it (fan_invalidate): batch-wide.  So a move carries
+// neither: an imported session has no valid branch, as a restarted one.
 void fanout_planes(const rb_p2p* b, PlaneSet& ps) {
-  if (b->spec_meta) ps.fill(b->spec_meta, 4, SM_COUNT, 1, 0);
+  if (!b->spec_meta) return;
+  ps.fill(b->spec_meta, 4, SM_COUNT, 1, 0);
+  ps.fresh_on_move();
 }
 // ConnectionStatus::default for every (endpoint, player)
 void peer_planes(const rb_p2p* b, PlaneSet& ps) {
@@ -342,10 +352,17 @@ void desync_planes(const rb_p2p* b, PlaneSet& ps) {
   ps.fill(d.ev_n, 4, 1, 1, 0);
   ps.fill(d.ev_frame, 4, kEvents, 1, 0xff);
   ps.fill(d.ev_handle, 4, kEvents, 1, 0xff);
+  // the entries behind those counts and frames: no fresh value, a move carries them
+  ps.carried(d.rh_lo, 8, 4 * kCsHist, 1);
+  ps.carried(d.rh_hi, 8, 4 * kCsHist, 1);
+  ps.carried(d.ob_frame, 4, kOutbox, 1);
+  ps.carried(d.ob_cs, 8, kOutbox, 1);
+  ps.carried(d.ev_local, 8, kEvents, 1);
+  ps.carried(d.ev_remote, 8, kEvents, 1);
 }
 // next_spectator_frame = 0 (p2p_session.rs:201), status RB_P2P_EXPORT_OK
 void export_planes(const rb_p2p* b, PlaneSet& ps) {
-  if (b->exp_state) ps.fill(b->exp_state, 4, 2, 1, 0);
+  if (b->exp_state || ps.layout_only) ps.fill(b->exp_state, 4, 2, 1, 0);
 }
 // TimeSync::default, local / remote_frame_advantage 0, round_trip_time 0, next_recommended_sleep 0,
 // frames_ahead 0, no event
@@ -356,7 +373,7 @@ void time_sync_planes(const rb_p2p* b, PlaneSet& ps) {
 }
 // nothing parked yet, acc = 0
 void pace_planes(const rb_p2p* b, PlaneSet& ps) {
-  if (!b->pace.view) return;
+  if (!b->pace.view && !(ps.layout_only && !b->fanout)) return;  // a fan-out batch never paces
   ps.fill(b->pace.view, 4, 1, 1, 0);
   ps.fill(b->pace.parked, 4, 1, 1, 0);
   ps.fill(b->pace.acc, 4, 1, 1, 0);
@@ -389,6 +406,13 @@ rb_status pace_reserve(rb_p2p* b) {
   P2P_TRY(b, hipMalloc(&b->pace.parked, bytes));
   P2P_TRY(b, hipMalloc(&b->pace.acc, bytes));
   P2P_TRY(b, fill_group(b, pace_planes));
+  return RB_OK;
+}
+// The export's rows, made by the first call that needs them.
+rb_status export_reserve(rb_p2p* b) {
+  if (b->exp_state) return RB_OK;
+  P2P_TRY(b, hipMalloc(&b->exp_state, 2 * static_cast<size_t>(b->Spad) * 4));
+  P2P_TRY(b, fill_group(b, export_planes));
   return RB_OK;
 }
 template <int IB>
@@ -983,13 +1007,14 @@ rb_status rb_p2p_run_ticks_packets(rb_p2p* b, int32_t n_ticks, const void* local
 rb_status rb_p2p_disconnect_player(rb_p2p* b, int32_t handle, const uint8_t* session_mask) {
   if (handle < 0 || handle >= b->P) return pfail(b, RB_INVALID_REQUEST, "Invalid Player Handle.");
   if ((b->cfg.local_mask >> handle) & 1u) return pfail(b, RB_INVALID_REQUEST, "Local Player cannot be disconnected.");
-  if (b->peer.on) {  // peers' reports disconnect players inside the ticks: refresh the mirror
+  if (b->peer.on || b->mirror_stale) {  // peers' reports disconnect players inside the ticks, an import brings its own: refresh the mirror
     std::vector<int32_t> qs;
     rb_status r = read_rows(b, b->qs, kQsFields, qs);
     if (r != RB_OK) return r;
     for (int h = 0; h < b->P; ++h)
       for (int s = 0; s < b->S; ++s)
         b->disconnected[static_cast<size_t>(h) * b->S + s] = (static_cast<uint32_t>(qs[(QS_PLAYER0 + QF_MISC * 4 + h) * b->Spad + s]) & kQmDisc) != 0;
+    b->mirror_stale = false;
   }
   uint8_t* d = b->disconnected.data() + static_cast<size_t>(handle) * b->S;
   for (int s = 0; s < b->S; ++s)
@@ -1028,6 +1053,94 @@ rb_status rb_p2p_restart_sessions(rb_p2p* b, const uint8_t* session_mask) {
   else
     for (int h = 0; h < b->P; ++h)
       for (int32_t s : idx) b->disconnected[static_cast<size_t>(h) * b->S + s] = 0;
+  return RB_OK;
+}
+
+// ---- moving sessions between batches (migrate.hpp).  GGRS has no such call: a P2PSession is an
+// ordinary movable Rust value.
+
+// The configuration the kernels compile in or read: a record goes only into a batch that agrees.
+static std::vector<uint32_t> record_config(const rb_p2p* b) {
+  const GameOps& o = *b->ops;
+  return {1u /* a P2P batch */,
+          static_cast<uint32_t>(b->cfg.game),
+          static_cast<uint32_t>(b->P),
+          static_cast<uint32_t>(b->W),
+          static_cast<uint32_t>(o.input_bytes),
+          static_cast<uint32_t>(o.nw),
+          static_cast<uint32_t>(o.lanes),
+          static_cast<uint32_t>(o.cs_bytes),
+          static_cast<uint32_t>(o.image_bytes),
+          static_cast<uint32_t>(b->cfg.input_delay),
+          static_cast<uint32_t>(b->cfg.remote_delay),
+          b->cfg.local_mask,
+          b->cfg.sparse_saving ? 1u : 0u,
+          static_cast<uint32_t>(b->ds.interval),
+          b->peer.on ? 1u : 0u,
+          b->ts_on ? 1u : 0u,
+          b->ts_on ? static_cast<uint32_t>(b->ts.fps) : 0u,
+          b->fanout ? (b->per_player ? 2u : 1u) : 0u,
+          b->fanout ? static_cast<uint32_t>(b->cfg.fanout_candidates) : 0u};
+}
+
+// Every per-session plane the batch's configuration can have, the carry-only ones included.
+// layout_only: without making the lazily made groups (their planes have no buffers).
+static RecordLayout record_planes(const rb_p2p* b, PlaneSet& ps, bool layout_only) {
+  ps.carry = true;
+  ps.layout_only = layout_only;
+  all_planes(b, ps);
+  return record_layout(plane_shapes(ps), record_config(b));
+}
+
+static rb_status move_sessions(rb_p2p* b, const int32_t* sessions, int32_t n, void* records, bool scatter) {
+  const char* const who = scatter ? "rb_p2p_import_sessions" : "rb_p2p_export_sessions";
+  if (n < 0 || (n > 0 && (!sessions || !records))) return pfail(b, RB_INVALID_REQUEST, std::string(who) + ": missing session list or records");
+  if (!move_indices_ok(sessions, n, b->S))
+    return pfail(b, RB_INVALID_REQUEST, std::string(who) + ": sessions must be distinct indices in [0, num_sessions)");
+  if (n == 0) return RB_OK;
+  if (reinterpret_cast<uintptr_t>(records) % 16 != 0)
+    return pfail(b, RB_INVALID_REQUEST, std::string(who) + ": records need 16-byte alignment");
+  DeviceScope dev_scope(b->device);
+  // the groups a later call would make, with create's fresh values: record_bytes depends on the
+  // configuration only, and no read-back of a batch that never paces or exports changes
+  rb_status r = export_reserve(b);
+  if (r == RB_OK && !b->fanout) r = pace_reserve(b);
+  if (r != RB_OK) return r;
+  if (scatter && !b->refused) {
+    P2P_TRY(b, hipMalloc(&b->refused, 4));
+    P2P_TRY(b, hipMemsetAsync(b->refused, 0, 4, b->stream));
+  }
+  PlaneSet ps;
+  const RecordLayout lay = record_planes(b, ps, false);
+  P2P_TRY(b, b->move_idx.upload(std::vector<int32_t>(sessions, sessions + n), static_cast<size_t>(b->S), b->stream));
+  P2P_TRY(b, move_launch(ps, lay, b->move_idx.dev, static_cast<uint32_t>(n), records, scatter, b->refused, b->stream));
+  if (scatter) {
+    b->ticked = true;        // the columns hold a running match: rb_p2p_time_sync_enable is closed
+    b->mirror_stale = true;  // ConnectionStatus::disconnected arrived in qs
+  }
+  return RB_OK;
+}
+
+int64_t rb_p2p_session_record_bytes(const rb_p2p* b) {
+  PlaneSet ps;
+  return static_cast<int64_t>(record_planes(b, ps, true).record_bytes);
+}
+
+rb_status rb_p2p_export_sessions(rb_p2p* b, const int32_t* sessions, int32_t n, void* records_dev) {
+  return move_sessions(b, sessions, n, records_dev, false);
+}
+
+rb_status rb_p2p_import_sessions(rb_p2p* b, const int32_t* sessions, int32_t n, const void* records_dev) {
+  return move_sessions(b, sessions, n, const_cast<void*>(records_dev), true);
+}
+
+rb_status rb_p2p_import_refused(rb_p2p* b, uint32_t* count) {
+  if (!count) return RB_OK;
+  *count = 0;
+  if (!b->refused) return RB_OK;  // no import yet
+  DeviceScope dev_scope(b->device);
+  P2P_TRY(b, hipMemcpyAsync(count, b->refused, 4, hipMemcpyDeviceToHost, b->stream));
+  P2P_TRY(b, hipStreamSynchronize(b->stream));
   return RB_OK;
 }
 
@@ -1181,10 +1294,7 @@ rb_status rb_p2p_export_confirmed_inputs(rb_p2p* b, void* inputs_by_frame, int32
   if (!inputs_by_frame || !upto || !last_frames || !disconnected || frames <= 0)
     return pfail(b, RB_INVALID_REQUEST, "rb_p2p_export_confirmed_inputs: missing output tensor");
   DeviceScope dev_scope(b->device);
-  if (!b->exp_state) {
-    P2P_TRY(b, hipMalloc(&b->exp_state, 2 * static_cast<size_t>(b->Spad) * 4));
-    P2P_TRY(b, fill_group(b, export_planes));
-  }
+  if (rb_status r = export_reserve(b); r != RB_OK) return r;
   const dim3 grid((b->S + 255) / 256), block(256);
   auto k = b->ops->input_bytes == 4 ? p2p_export_kernel<4> : p2p_export_kernel<1>;
   if (b->ops->input_bytes != 4 && b->ops->input_bytes != 1)

@@ -82,9 +82,21 @@ inline size_t restart_word_index(int NW, size_t cols, size_t c, int k) {
 
 // A batch's planes under construction: the descriptors, and the template words they refer to by
 // offset until bind() points them into the device copy of `tmpl`.
+//
+// A plane has one of three kinds.  Most have a fresh value, which create and restart write and a
+// move (migrate.hpp) carries.  A carry-only plane has none: its stale content is harmless to a
+// fresh session (entries behind a count or a NULL frame are never read), so it is listed only when
+// `carry` is set, which a move does and create and restart do not: restart_kernel's table is what
+// it was.  A fresh-on-move plane is written by create and restart but not carried: the record holds
+// its fresh value (a fill byte), so an imported session has it as a restarted one does.
+enum : uint8_t { kPlaneFresh = 0, kPlaneCarryOnly = 1, kPlaneFreshOnMove = 2 };
+
 struct PlaneSet {
   size_t Spad = 0;
+  bool carry = false;        // list the carry-only planes too
+  bool layout_only = false;  // list the groups a later call makes as well, with no buffers: for a record's layout
   std::vector<RestartPlane> planes;
+  std::vector<uint8_t> kind;  // per plane
   std::vector<uint32_t> tmpl;
   std::vector<size_t> tmpl_off;  // per plane: byte offset into tmpl, or npos
 
@@ -103,8 +115,17 @@ struct PlaneSet {
     q.src_cols = 1;
     q.fill = fill_byte;
     planes.push_back(q);
+    kind.push_back(kPlaneFresh);
     tmpl_off.push_back(npos);
   }
+  // [rows][Spad * cps] elements with no fresh value: carried by a move, skipped otherwise
+  void carried(void* base, int esize, size_t rows, int cps) {
+    if (!carry) return;
+    fill(base, esize, rows, cps, 0);
+    kind.back() = kPlaneCarryOnly;
+  }
+  // the last plane (a fill) is not carried by a move: the record holds its fresh value
+  void fresh_on_move() { kind.back() = kPlaneFreshOnMove; }
   // [groups][rows][Spad] words, row r of every group `values[r]`
   void row_values(int32_t* base, size_t groups, const std::vector<int32_t>& values) {
     fill(base, 4, values.size(), 1, 0);
@@ -191,7 +212,7 @@ struct RestartIndex {
   }
 };
 
-// restart_kernel over `set` (bound) for the n sessions idx[0..n) (device memory; nullptr: 0..n-1).
+// restart_kernel over `set` (bound, without carry-only planes) for the n sessions idx[0..n) (device memory; nullptr: 0..n-1).
 // One launch, stream ordered.  hipErrorInvalidValue: more than kRestartMaxPlanes planes.
 hipError_t restart_launch(const PlaneSet& set, const int32_t* idx, uint32_t n, hipStream_t stream);
 
@@ -240,7 +261,7 @@ __global__ void __launch_bounds__(256) restart_kernel(const RestartTable t) {
 
 hipError_t restart_launch(const PlaneSet& set, const int32_t* idx, uint32_t n, hipStream_t stream) {
   if (n == 0 || set.planes.empty()) return hipSuccess;
-  if (set.planes.size() > static_cast<size_t>(kRestartMaxPlanes)) return hipErrorInvalidValue;
+  if (set.planes.size() > static_cast<size_t>(kRestartMaxPlanes) || set.carry) return hipErrorInvalidValue;
   RestartTable t{};
   uint32_t chunks = 0, cps = 1;
   for (t.rows_per = kRestartRows;; t.rows_per *= 2) {  // more rows per thread until the chunks fit the table

@@ -6,7 +6,7 @@
 #include <vector>
 
 #include "kernels.hpp"
-#include "restart.hpp"
+#include "migrate.hpp"
 
 using namespace rb;
 
@@ -25,6 +25,8 @@ struct rb_spectator {
   uint32_t* counters = nullptr;         // [1] unexpected math paths
   uint32_t* tmpl = nullptr;             // the fresh columns restart_kernel copies (restart.hpp PlaneSet::tmpl)
   RestartIndex restart_idx;             // rb_spectator_restart_sessions' selected sessions
+  RestartIndex move_idx;                // rb_spectator_export_sessions' / rb_spectator_import_sessions'
+  uint32_t* refused = nullptr;          // [1] records rb_spectator_import_sessions refused since create
   std::string last_err;
 };
 
@@ -61,6 +63,8 @@ void free_all(rb_spectator* b) {
   for (void* q : ptrs)
     if (q) (void)hipFree(q);
   b->restart_idx.release();
+  b->move_idx.release();
+  if (b->refused) (void)hipFree(b->refused);
   if (b->own_stream) (void)hipStreamDestroy(b->own_stream);
 }
 
@@ -232,6 +236,62 @@ rb_status rb_spectator_restart_sessions(rb_spectator* b, const uint8_t* session_
   if (!all) SPT_TRY(b, b->restart_idx.upload(idx, static_cast<size_t>(b->S), b->stream));
   SPT_TRY(b, restart_launch(ps, all ? nullptr : b->restart_idx.dev, all ? static_cast<uint32_t>(b->S) : static_cast<uint32_t>(idx.size()),
                             b->stream));
+  return RB_OK;
+}
+
+// ---- moving spectators between batches (migrate.hpp), as rb_p2p_export_sessions moves their hosts.
+// Every plane of spectator_planes is carried: live state, checksum, frames, status, host status.
+static RecordLayout record_planes(const rb_spectator* b, PlaneSet& ps) {
+  ps.carry = true;
+  spectator_planes(b, ps);
+  const GameOps& o = *b->ops;
+  return record_layout(plane_shapes(ps),
+                       {2u /* a spectator batch */, static_cast<uint32_t>(b->cfg.game), static_cast<uint32_t>(b->P),
+                        static_cast<uint32_t>(o.input_bytes), static_cast<uint32_t>(o.nw), static_cast<uint32_t>(o.lanes),
+                        static_cast<uint32_t>(o.cs_bytes), static_cast<uint32_t>(o.image_bytes),
+                        static_cast<uint32_t>(b->cfg.max_frames_behind), static_cast<uint32_t>(b->cfg.catchup_speed)});
+}
+
+static rb_status move_sessions(rb_spectator* b, const int32_t* sessions, int32_t n, void* records, bool scatter) {
+  const char* const who = scatter ? "rb_spectator_import_sessions" : "rb_spectator_export_sessions";
+  if (n < 0 || (n > 0 && (!sessions || !records))) return sfail(b, RB_INVALID_REQUEST, std::string(who) + ": missing session list or records");
+  if (!move_indices_ok(sessions, n, b->S))
+    return sfail(b, RB_INVALID_REQUEST, std::string(who) + ": sessions must be distinct indices in [0, num_sessions)");
+  if (n == 0) return RB_OK;
+  if (reinterpret_cast<uintptr_t>(records) % 16 != 0)
+    return sfail(b, RB_INVALID_REQUEST, std::string(who) + ": records need 16-byte alignment");
+  DeviceScope dev_scope(b->device);
+  if (scatter && !b->refused) {
+    SPT_TRY(b, hipMalloc(&b->refused, 4));
+    SPT_TRY(b, hipMemsetAsync(b->refused, 0, 4, b->stream));
+  }
+  PlaneSet ps;
+  const RecordLayout lay = record_planes(b, ps);
+  SPT_TRY(b, b->move_idx.upload(std::vector<int32_t>(sessions, sessions + n), static_cast<size_t>(b->S), b->stream));
+  SPT_TRY(b, move_launch(ps, lay, b->move_idx.dev, static_cast<uint32_t>(n), records, scatter, b->refused, b->stream));
+  return RB_OK;
+}
+
+int64_t rb_spectator_session_record_bytes(const rb_spectator* b) {
+  PlaneSet ps;
+  return static_cast<int64_t>(record_planes(b, ps).record_bytes);
+}
+
+rb_status rb_spectator_export_sessions(rb_spectator* b, const int32_t* sessions, int32_t n, void* records_dev) {
+  return move_sessions(b, sessions, n, records_dev, false);
+}
+
+rb_status rb_spectator_import_sessions(rb_spectator* b, const int32_t* sessions, int32_t n, const void* records_dev) {
+  return move_sessions(b, sessions, n, const_cast<void*>(records_dev), true);
+}
+
+rb_status rb_spectator_import_refused(rb_spectator* b, uint32_t* count) {
+  if (!count) return RB_OK;
+  *count = 0;
+  if (!b->refused) return RB_OK;  // no import yet
+  DeviceScope dev_scope(b->device);
+  SPT_TRY(b, hipMemcpyAsync(count, b->refused, 4, hipMemcpyDeviceToHost, b->stream));
+  SPT_TRY(b, hipStreamSynchronize(b->stream));
   return RB_OK;
 }
 

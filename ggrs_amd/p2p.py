@@ -17,6 +17,7 @@ import enum
 import numpy as np
 
 from . import _lib as L
+from .migrate import _Movable
 from .session import DeviceError, InvalidRequest, Panic, _StreamOrdered, input_dtype
 from .synth import SEED, splitmix64
 
@@ -35,7 +36,7 @@ def _dev_ptr(x):
     return ctypes.c_void_p(x.data_ptr()), x
 
 
-class P2PSession(_StreamOrdered):
+class P2PSession(_Movable, _StreamOrdered):
     """p2p_session.rs:116-929 (rollback path) for ``num_sessions`` sessions.
 
     Device work runs on the batch's own HIP stream (or the one set_stream
@@ -43,6 +44,8 @@ class P2PSession(_StreamOrdered):
     (_StreamOrdered): inputs made on torch's stream are complete before a
     launch reads them, and tensors a call writes (checksum reports) are
     complete before later torch work on the current stream reads them."""
+
+    _MOVE = "rb_p2p"  # export_sessions, import_sessions, import_refused, record_bytes (migrate.py)
 
     def __init__(self, lib, handle, game, cfg):
         self._lib = lib

@@ -16,17 +16,20 @@ import ctypes
 import numpy as np
 
 from . import _lib as L
+from .migrate import _Movable
 from .p2p import _dev_ptr
 from .session import (DeviceError, InvalidRequest, Panic, PredictionThreshold, SpectatorTooFarBehind, _StreamOrdered,
                       input_dtype)
 
 
-class SpectatorSession(_StreamOrdered):
+class SpectatorSession(_Movable, _StreamOrdered):
     """p2p_spectator_session.rs:22-254 for ``num_sessions`` sessions that start Running.
 
     Device work runs on the batch's own HIP stream (or the one set_stream
     chose), ordered against torch's current stream at every call
     (_StreamOrdered)."""
+
+    _MOVE = "rb_spectator"  # export_sessions, import_sessions, import_refused, record_bytes (migrate.py)
 
     def __init__(self, lib, handle, game, cfg):
         self._lib = lib

@@ -440,6 +440,57 @@ rb_status rb_p2p_disconnect_player(rb_p2p* b, int32_t handle, const uint8_t* ses
  * closed. */
 rb_status rb_p2p_restart_sessions(rb_p2p* b, const uint8_t* session_mask);
 
+/* Moving running sessions between batches.  GGRS has no such call, because a
+ * P2PSession is an ordinary movable Rust value; here a session is a column of
+ * every per-session buffer of its batch, and a move is an export of the
+ * selected columns into session records and an import of records into the
+ * selected columns of another batch (or of the same one: a rewind), on another
+ * device or in another process if the caller carries the bytes there.
+ *
+ * A record is a position-independent byte image of one session
+ * (ggrs_amd/csrc/session_record.hpp): a 32-byte header
+ * (magic, format version, record_bytes, a fingerprint of the batch's plane
+ * list and configuration) and every per-session value: all that
+ * rb_p2p_restart_sessions resets, and the checksum history, outbox and
+ * desync-event payloads behind their counts.  records_dev is device memory,
+ * [n][record_bytes] bytes, 16-byte aligned; record k belongs to sessions[k].
+ * Records stand on their own: they may be reordered, copied through the host,
+ * sent elsewhere or written to disk.  rb_p2p_session_record_bytes depends on
+ * the batch's configuration alone (a multiple of 16).
+ *
+ * `sessions` is a host list of n distinct indices in [0, S), consumed before
+ * the call returns; a duplicate or an index out of range is
+ * RB_INVALID_REQUEST, refused before any launch; n == 0 is RB_OK without a
+ * launch.  Both calls go between rb_p2p_run_ticks calls, are stream ordered on
+ * the batch's stream and do not synchronise the host.  Both make the pacing
+ * rows and the export's rows if the batch has not used them yet, with create's
+ * fresh values (no read-back changes).
+ *
+ * Export only reads the batch.  Import overwrites the selected sessions'
+ * columns and no others.  It checks every record's header on the device
+ * against this batch's magic, version, record_bytes and fingerprint: game,
+ * num_players, max_prediction, input and state sizes, input and remote delay,
+ * local_mask, sparse_saving, desync_interval, RB_P2P_FLAG_PEER_STATUS, time
+ * sync on / off and its fps, and the fan-out mode and candidates must agree.
+ * A record that does not match leaves its session untouched, in every buffer,
+ * and adds 1 to a count rb_p2p_import_refused reads (since create;
+ * synchronises).
+ *
+ * A moved session keeps its own frame numbering: the caller's tensors move
+ * with it (the session's columns of remote_inputs, remote_upto, packet start
+ * frames, the export rows, its spectators' host_upto).  After an import
+ * rb_p2p_time_sync_enable is closed as after a tick, and the next
+ * rb_p2p_disconnect_player reads the imported connect status back first.
+ * Batch-wide values stay with their batch: rb_p2p_counters, rb_p2p_totals, the
+ * adaptive fan-out's policy, the launch clock.  Of a fan-out batch the
+ * presimulated branches are not carried: an imported session has no valid
+ * branch, as a restarted one, and its next confirmation rolls back; states are
+ * identical, only rb_p2p_totals differ. */
+int64_t   rb_p2p_session_record_bytes(const rb_p2p* b);
+rb_status rb_p2p_export_sessions(rb_p2p* b, const int32_t* sessions, int32_t n, void* records_dev);
+rb_status rb_p2p_import_sessions(rb_p2p* b, const int32_t* sessions, int32_t n, const void* records_dev);
+rb_status rb_p2p_import_refused(rb_p2p* b, uint32_t* count);   /* read-back: synchronises */
+
 /* Per session, the last tick: rb_status of its advance_frame, the LoadGameState
  * frame (RB_NULL_FRAME: no rollback), AdvanceFrame and SaveGameState counts.
  * Any pointer may be NULL.  Synchronises. */
@@ -743,6 +794,17 @@ rb_status rb_spectator_receive_host_status(rb_spectator* b, const int32_t* last_
  * so the spectator follows its host's next match from frame 0.  Unselected
  * sessions are untouched; rb_spectator_totals continues since create. */
 rb_status rb_spectator_restart_sessions(rb_spectator* b, const uint8_t* session_mask);
+
+/* rb_p2p_export_sessions / rb_p2p_import_sessions for spectators: a spectator
+ * moves with its host by the same calls on its own batch.  Its record holds
+ * the live state and checksum, current and last received frame, the last
+ * status and the host connect status; the fingerprint covers game,
+ * num_players, the input and state sizes, max_frames_behind and
+ * catchup_speed.  rb_spectator_totals stays with the batch. */
+int64_t   rb_spectator_session_record_bytes(const rb_spectator* b);
+rb_status rb_spectator_export_sessions(rb_spectator* b, const int32_t* sessions, int32_t n, void* records_dev);
+rb_status rb_spectator_import_sessions(rb_spectator* b, const int32_t* sessions, int32_t n, const void* records_dev);
+rb_status rb_spectator_import_refused(rb_spectator* b, uint32_t* count);   /* read-back: synchronises */
 
 /* n_ticks x SpectatorSession::advance_frame (+ handle_requests) for every
  * session, in ONE device launch.  Device pointers, stream ordered:
