@@ -32,6 +32,7 @@
 
 #include "games.hpp"
 #include "p2p_variant.hpp"
+#include "wire_varint.hpp"
 
 namespace rb {
 
@@ -1627,19 +1628,8 @@ p2p_kernel(const P2PParams p) {
         };
         bool ok = true;
         while (pos < n) {
-          uint32_t hdr = 0;
-          int shift = 0;
-          bool done = false;
-          while (pos < n && shift < 35) {  // LEB128
-            const uint32_t b = next();
-            hdr |= (b & 0x7Fu) << shift;
-            shift += 7;
-            if (!(b & 0x80u)) {
-              done = true;
-              break;
-            }
-          }
-          if (!done) {
+          uint32_t hdr;
+          if (!rb_wire::varint_get(pos, n, next, hdr)) {  // LEB128 (wire_varint.hpp)
             ok = false;
             break;
           }

@@ -18,6 +18,7 @@
 #include <string>
 
 #include "../../include/ggrs_amd.h"
+#include "wire_varint.hpp"
 
 namespace {
 
@@ -104,43 +105,44 @@ __global__ void __launch_bounds__(256) decode_packets_kernel(const DecParams p) 
     }
     ++k;
   };
-  int32_t pos = 0;
+  // pass 0 validates without writing, pass 1 writes: a malformed packet (the reference panics before
+  // any input is added, protocol.rs:656) leaves remote_inputs as it found them
   bool ok = true;
-  while (pos < n && ok) {
-    uint32_t hdr = 0;
-    int shift = 0;
-    bool done = false;
-    while (pos < n && shift < 35) {  // LEB128
-      const uint8_t b = d[pos++];
-      hdr |= static_cast<uint32_t>(b & 0x7F) << shift;
-      shift += 7;
-      if (!(b & 0x80)) {
-        done = true;
-        break;
-      }
-    }
-    if (!done) {
-      ok = false;
-      break;
-    }
-    if (hdr & 1u) {  // compressed run of 0x00 / 0xFF
-      const uint32_t len = hdr >> 2;
-      if (len > (1u << 16)) {
+  for (int pass = 0; pass < 2 && ok; ++pass) {
+    int32_t pos = 0;
+    uint32_t nbytes = 0;  // pass 0: the XOR stream's length (mod 2^32: only its remainder by IB is read)
+    while (pos < n && ok) {
+      uint32_t hdr;
+      if (!rb_wire::varint_get(pos, n, [&]() -> uint32_t { return d[pos++]; }, hdr)) {  // LEB128
         ok = false;
         break;
       }
-      const uint8_t x = (hdr & 2u) ? 0xFF : 0x00;
-      for (uint32_t i = 0; i < len; ++i) emit(x);
-    } else {  // literal bytes
-      const uint32_t len = hdr >> 1;
-      if (len > static_cast<uint32_t>(n - pos)) {
-        ok = false;
-        break;
+      if (hdr & 1u) {  // compressed run of 0x00 / 0xFF
+        const uint32_t len = hdr >> 2;
+        if (len > (1u << 16)) {
+          ok = false;
+          break;
+        }
+        const uint8_t x = (hdr & 2u) ? 0xFF : 0x00;
+        if (pass == 0) nbytes += len;
+        else
+          for (uint32_t i = 0; i < len; ++i) emit(x);
+      } else {  // literal bytes
+        const uint32_t len = hdr >> 1;
+        if (len > static_cast<uint32_t>(n - pos)) {
+          ok = false;
+          break;
+        }
+        if (pass == 0) {
+          nbytes += len;
+          pos += static_cast<int32_t>(len);
+        } else {
+          for (uint32_t i = 0; i < len; ++i) emit(d[pos++]);
+        }
       }
-      for (uint32_t i = 0; i < len; ++i) emit(d[pos++]);
     }
+    if (pass == 0 && nbytes % static_cast<uint32_t>(IB) != 0) ok = false;  // compression.rs:47 assert: whole inputs only
   }
-  if (ok && k % IB != 0) ok = false;  // compression.rs:47 assert: whole inputs only
   if (!ok) {
     p.status[s] = kDecMalformed;  // the reference panics ("decoding failed", protocol.rs:656)
     return;

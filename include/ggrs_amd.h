@@ -42,7 +42,13 @@ typedef enum rb_status {
   RB_PANIC = 101                   /* a reference assert!/panic! condition was hit (API misuse) */
 } rb_status;
 
-/* Compiled-in game handlers (the `Config` trait's State/Input + handle_requests). */
+/* Compiled-in game handlers (the `Config` trait's State/Input + handle_requests).
+ * Input domain: every value of the input type is a legal input, as in the reference
+ * (its inputs are Pod).  ex_game's State::advance reads bits 0-3 of its byte, while the
+ * InputQueue compares, predicts and ships the whole byte: SyncTest, P2P (plain, sparse,
+ * every fan-out form, packet-fed), spectators and the brawler's fan-out are tested over
+ * all 256 byte values, the stub game over any u32 (tests/test_input_domain.py,
+ * tests/test_wire_edges.py). */
 typedef enum rb_game {
   RB_GAME_EX_GAME = 1,        /* examples/ex_game/ex_game.rs: f32 ships, Input{inp:u8}, fletcher16 over the bincode image */
   RB_GAME_STUB = 2,           /* tests/stubs.rs GameStub: i32 state, StubInput{inp:u32}, SipHash-1-3 checksum */
@@ -860,9 +866,20 @@ int32_t rb_spectator_input_bytes(const rb_spectator* b);
  * status[s]: 0 new inputs, 1 nothing new, -1 malformed (the reference panics:
  * "decoding failed"; also a length above packet_stride), -2 frames missing
  * before start_frame (the reference asserts).  The caller decides what a
- * negative status does to the session (nothing is decoded for it).
+ * negative status does to the session (nothing is decoded for it: the packet
+ * is validated as a whole before its first input is written).
  * A packet whose reference input is older than 2*max_prediction frames is
- * ignored (recv_inputs retention, protocol.rs:686-688). */
+ * ignored (recv_inputs retention, protocol.rs:686-688).  Inputs of frames at or
+ * above remote_frames are not written, and remote_upto stops at the last frame
+ * written.
+ * Segment headers are unsigned LEB128 varints (csrc/wire_varint.hpp, shared with the
+ * decoder inside rb_p2p_run_ticks_packets).  Accepted: up to ten bytes whose value is
+ * below 2^32, so a header padded with continuation groups of zero payload (0x80 ...
+ * 0x00) past its fifth byte decodes like its short form, and payload bits 1-6 of a
+ * tenth byte (past bit 63) are dropped.  Malformed: a header cut off by the packet's
+ * end or still continued after ten bytes, and any header whose value reaches 2^32
+ * (bits 32-34 of the fifth byte, any payload bit of bytes six to nine, bit 0 of the
+ * tenth): it is neither a run of at most 65,536 bytes nor a literal that fits. */
 rb_status rb_decode_input_packets(int32_t device, void* stream, int32_t handle, int32_t num_players,
                                   int32_t num_sessions, int32_t input_bytes, int32_t max_prediction,
                                   const uint8_t* packets, int64_t packet_stride, const int32_t* lengths,

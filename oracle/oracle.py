@@ -392,6 +392,8 @@ def wire_decode(ref: bytes, data: bytes, cap: int = 4096):
     n = load().orc_wire_decode(_ptr(r), r.size, _ptr(d), len(data), _ptr(out), cap)
     if n == -1:
         return None
+    if n == -2 and cap < (1 << 20):  # more inputs than `cap`: a long run
+        return wire_decode(ref, data, cap * 32)
     assert n >= 0
     return out[:n]
 

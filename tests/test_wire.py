@@ -216,11 +216,11 @@ def test_gpu_p2p_fed_through_the_wire_equals_direct_delivery(gpu_available, P, m
     assert wired.totals()[2] > 0  # rollbacks happened on the wire-fed batch too
 
 
-def _encode_schedule(lib, P, S, T, mask, rd, upto, dr, stride, seed, max_redo=2):
+def _encode_schedule(lib, P, S, T, mask, rd, upto, dr, stride, seed, max_redo=2, ib=1):
     """Every tick's packets, encoded on the device ahead of the ticks: remote
     handle h sends frames acked+1 .. upto[t, h], acked = the frame it knows
     the receiver had one tick earlier minus 0-max_redo re-sent frames (an un-acked
-    sender); [T, P, S, stride] packets and [T, P, S] lengths / start frames."""
+    sender); [T, P, S, stride] packets and [T, P, S] lengths / start frames.  ib: bytes per input of dr."""
     import ctypes
 
     import torch
@@ -240,7 +240,7 @@ def _encode_schedule(lib, P, S, T, mask, rd, upto, dr, stride, seed, max_redo=2)
             acked = torch.where(prev < 0, prev, torch.clamp(prev - redo, min=rd - 1))
             acked = torch.where(acked < rd, torch.full_like(acked, -1), acked).contiguous()
             newest = du[t, h].contiguous()
-            assert lib.rb_encode_input_packets(0, None, h, P, S, 1, p(dr), F, rd, p(acked), p(newest), p(pk[t, h]),
+            assert lib.rb_encode_input_packets(0, None, h, P, S, ib, p(dr), F, rd, p(acked), p(newest), p(pk[t, h]),
                                                stride, p(ln[t, h]), p(st[t, h])) == 0
     torch.cuda.synchronize()
     assert int((ln < 0).sum()) == 0
@@ -338,13 +338,14 @@ def test_gpu_malformed_packet_panics_only_its_session(gpu_available):
         wired.run_ticks_packets(di[:1], pk[:1, :, :, :16], ln[:1], st[:1])
 
 
-def _oracle_packet_deliveries(P, S, T, mask, W, F, pk, ln, st):
+def _oracle_packet_deliveries(P, S, T, mask, W, F, pk, ln, st, ib=1):
     """UdpProtocol::on_input (protocol.rs:616-689) restated on the host for every tick's packet
     of every remote endpoint (on_input_reference): per tick the receiver's newest frame per
     endpoint and its inputs by frame, exactly what the oracle's P2PSession is then delivered;
-    plus the decode status per (tick, handle, session)."""
+    plus the decode status per (tick, handle, session).  ib: bytes per input."""
     pk_h, ln_h, st_h = pk.cpu().numpy(), ln.cpu().numpy(), st.cpu().numpy()
-    recv = np.zeros((F, P, S), np.uint8)
+    recv = np.zeros((F, P, S), {1: np.uint8, 2: np.uint16, 4: np.uint32}[ib])
+    raw = recv.view(np.uint8).reshape(F, P, S, ib)  # the same memory, byte by byte
     last = np.full((P, S), -1, np.int32)
     uptos = np.full((T, P, S), -1, np.int32)
     codes = np.ones((T, P, S), np.int32)
@@ -356,11 +357,11 @@ def _oracle_packet_deliveries(P, S, T, mask, W, F, pk, ln, st):
             for s_ in range(S):
                 n = int(ln_h[t, h, s_])
                 start = int(st_h[t, h, s_])
-                refin = bytes([recv[start - 1, h, s_]]) if start >= 1 else bytes(1)
-                out, nl, code = on_input_reference(int(last[h, s_]), start, pk_h[t, h, s_, :n].tobytes(), refin, W, 1)
+                refin = raw[start - 1, h, s_].tobytes() if start >= 1 else bytes(ib)
+                out, nl, code = on_input_reference(int(last[h, s_]), start, pk_h[t, h, s_, :n].tobytes(), refin, W, ib)
                 codes[t, h, s_] = code
                 for f, b in out.items():
-                    recv[f, h, s_] = b[0]
+                    raw[f, h, s_] = np.frombuffer(b, np.uint8)
                 last[h, s_] = nl
         uptos[t] = last
         recvs.append(recv.copy())
