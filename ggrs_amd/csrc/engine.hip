@@ -174,11 +174,10 @@ struct rb_batch {
   bool live_valid = true;
   int32_t display_frame = kNullFrame;
   uint32_t tick = 0;
+  DeviceOwner res;  // every device buffer, pinned buffer and event of the batch
   // profiling
   bool prof = false;
-  std::vector<std::pair<hipEvent_t, hipEvent_t>> prof_ev;  // pool, reused after rb_profile_take
-  std::vector<int32_t> prof_ticks;                          // ticks covered by each timed launch
-  size_t prof_used = 0;
+  EventPool prof_ev{res};  // reused after rb_profile_take
   uint32_t prof_every = 8, prof_tick = 0;
   bool staged = false;  // this tick's inputs went through the host staging buffer
   std::string last_err;
@@ -190,44 +189,16 @@ struct rb_batch {
   uint32_t simds = 1024;  // SIMDs of the device (MI355X: 256 CUs x 4)
   uint32_t lds_pad = 0;  // RB_LDS_PAD (bytes) at create: dynamic LDS reserved per steady workgroup (A/B)
   LaunchClock clock;  // rb_launch_clock_arm
+  ~rb_batch() {
+    if (!own_stream) return;  // a plan-only batch, or nothing was made
+    (void)hipSetDevice(device);
+    (void)hipStreamSynchronize(stream);
+    res.release_all();
+    (void)hipStreamDestroy(own_stream);
+  }
 };
 
 namespace {
-thread_local std::string g_create_err;
-constexpr size_t kProfPool = 256;  // HIP event pairs created by rb_profile_enable
-
-rb_status fail(rb_batch* b, rb_status st, const std::string& msg) {
-  if (b) b->last_err = msg; else g_create_err = msg;
-  return st;
-}
-#define HIP_TRY(b, expr)                                                                          \
-  do {                                                                                            \
-    hipError_t _e = (expr);                                                                       \
-    if (_e != hipSuccess) return fail((b), RB_DEVICE_ERROR, std::string(#expr ": ") + hipGetErrorString(_e)); \
-  } while (0)
-
-rb_status destroy_device(rb_batch* b) {
-  if (b->plan_only) return RB_OK;
-  (void)hipSetDevice(b->device);
-  if (b->stream) (void)hipStreamSynchronize(b->stream);
-  void* ptrs[] = {b->snap, b->live, b->cs, b->fs, b->ring, b->last_cs, b->periodic_cs, b->err, b->live_frame,
-                  b->frozen, b->counters, b->stage_dev};
-  for (void* q : ptrs)
-    if (q) (void)hipFree(q);
-  if (b->stage_host) (void)hipHostFree(b->stage_host);
-  if (b->pinned_counters) (void)hipHostFree(const_cast<uint32_t*>(b->pinned_counters));
-  for (auto& e : b->stage_ev)
-    if (e) (void)hipEventDestroy(e);
-  if (b->tick_ev) (void)hipEventDestroy(b->tick_ev);
-  for (auto& pr : b->prof_ev) {
-    (void)hipEventDestroy(pr.first);
-    (void)hipEventDestroy(pr.second);
-  }
-  b->clock.release();
-  if (b->own_stream) (void)hipStreamDestroy(b->own_stream);
-  return RB_OK;
-}
-
 rb_status launch_program(rb_batch* b, const TickProgram& tp, bool ingest, bool display, int32_t periodic_step) {
   KParams p{};
   p.snap = b->snap;
@@ -277,36 +248,22 @@ rb_status launch_program(rb_batch* b, const TickProgram& tp, bool ingest, bool d
   p.debug = b->cfg.reserved[0];
   const bool timed = b->prof && (b->prof_tick++ % b->prof_every) == 0;  // sampled: an event pair costs host time
   LaunchEv ev;  // the kernel's own start / end (hipExtLaunchKernel), no marker packets around it
-  if (timed) {
-    if (b->prof_used == b->prof_ev.size()) {
-      hipEvent_t e0 = nullptr, e1 = nullptr;
-      HIP_TRY(b, hipEventCreate(&e0));
-      HIP_TRY(b, hipEventCreate(&e1));
-      b->prof_ev.push_back({e0, e1});
-    }
-    ev = LaunchEv{b->prof_ev[b->prof_used].first, b->prof_ev[b->prof_used].second};
-  }
-  HIP_TRY(b, b->ops->launch_tick(p, b->block, b->stream, ev));
-  if (timed) {
-    b->prof_ticks.resize(b->prof_ev.size());
-    b->prof_ticks[b->prof_used] = 1;
-    b->prof_used += 1;
-  }
+  if (timed) RB_TRY(b, b->prof_ev.next(ev));
+  RB_TRY(b, b->ops->launch_tick(p, b->block, b->stream, ev));
+  if (timed) b->prof_ev.commit(1);
   return RB_OK;
 }
 
 rb_status read_words_slot(rb_batch* b, const uint32_t* dev_base, std::vector<uint32_t>& host) {
   host.resize(static_cast<size_t>(b->ops->nw) * b->Spad * b->ops->lanes);
-  HIP_TRY(b, hipMemcpyAsync(host.data(), dev_base, host.size() * 4, hipMemcpyDeviceToHost, b->stream));
-  HIP_TRY(b, hipStreamSynchronize(b->stream));
+  RB_TRY(b, hipMemcpyAsync(host.data(), dev_base, host.size() * 4, hipMemcpyDeviceToHost, b->stream));
+  RB_TRY(b, hipStreamSynchronize(b->stream));
   return RB_OK;
 }
 
 // words [lanes][nw] of session s from a block of lane planes
 void words_of(const rb_batch* b, const std::vector<uint32_t>& planes, int s, uint32_t* w) {
-  const int L = b->ops->lanes, NW = b->ops->nw;
-  for (int l = 0; l < L; ++l)
-    for (int k = 0; k < NW; ++k) w[l * NW + k] = planes[word_index(NW, b->Spad * L, s * L + l, k)];
+  session_words(planes.data(), b->ops->nw, b->ops->lanes, b->Spad, s, w);
 }
 
 }  // namespace
@@ -395,84 +352,66 @@ rb_status rb_synctest_create(const rb_config* cfg, rb_batch** out) {
     *out = b.release();
     return RB_OK;
   }
-  rb_batch* bp = b.get();
-  auto hip_fail = [&](hipError_t e, const char* what) {
-    g_create_err = std::string(what) + ": " + hipGetErrorString(e);
-    destroy_device(bp);
-    return RB_DEVICE_ERROR;
-  };
-#define HIP_CREATE(expr)                          \
-  do {                                            \
-    hipError_t _e = (expr);                       \
-    if (_e != hipSuccess) return hip_fail(_e, #expr); \
-  } while (0)
-  HIP_CREATE(hipSetDevice(b->device));
+  // a failure from here on frees what was made (~rb_batch) and leaves its message for rb_last_error(nullptr)
+  RB_TRY(nullptr, hipSetDevice(b->device));
   int cus = 0;
-  HIP_CREATE(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, b->device));
+  RB_TRY(nullptr, hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, b->device));
   b->simds = 4 * cus;  // 4 SIMDs per CU (CDNA)
-  HIP_CREATE(hipStreamCreateWithFlags(&b->own_stream, hipStreamNonBlocking));
+  RB_TRY(nullptr, hipStreamCreateWithFlags(&b->own_stream, hipStreamNonBlocking));
   b->stream = b->own_stream;
   const size_t Sp = b->Spad, NW = b->ops->nw, W = b->W, L = b->ops->lanes, Gp = Sp * L;
-  HIP_CREATE(hipMalloc(&b->snap, W * NW * Gp * 4));
-  HIP_CREATE(hipMalloc(&b->live, NW * Gp * 4));
-  HIP_CREATE(hipMalloc(&b->cs, W * Sp * b->ops->cs_bytes));
-  HIP_CREATE(hipMalloc(&b->fs, W * Sp * b->ops->cs_bytes));
-  HIP_CREATE(hipMalloc(&b->ring, kQueueLen * Sp * b->ops->inrec_bytes));
-  HIP_CREATE(hipMalloc(&b->last_cs, Sp * b->ops->cs_bytes));
-  HIP_CREATE(hipMalloc(&b->periodic_cs, Sp * b->ops->cs_bytes));
-  HIP_CREATE(hipMalloc(&b->err, Sp * 4));
-  HIP_CREATE(hipMalloc(&b->live_frame, Sp * 4));
-  HIP_CREATE(hipMalloc(&b->frozen, Sp / 64 * 8));
-  HIP_CREATE(hipMalloc(&b->counters, 16));
+  RB_TRY(nullptr, b->res.alloc(b->snap, W * NW * Gp * 4));
+  RB_TRY(nullptr, b->res.alloc(b->live, NW * Gp * 4));
+  RB_TRY(nullptr, b->res.alloc(b->cs, W * Sp * b->ops->cs_bytes));
+  RB_TRY(nullptr, b->res.alloc(b->fs, W * Sp * b->ops->cs_bytes));
+  RB_TRY(nullptr, b->res.alloc(b->ring, kQueueLen * Sp * b->ops->inrec_bytes));
+  RB_TRY(nullptr, b->res.alloc(b->last_cs, Sp * b->ops->cs_bytes));
+  RB_TRY(nullptr, b->res.alloc(b->periodic_cs, Sp * b->ops->cs_bytes));
+  RB_TRY(nullptr, b->res.alloc(b->err, Sp * 4));
+  RB_TRY(nullptr, b->res.alloc(b->live_frame, Sp * 4));
+  RB_TRY(nullptr, b->res.alloc(b->frozen, Sp / 64 * 8));
+  RB_TRY(nullptr, b->res.alloc(b->counters, 16));
   const size_t stage = 2ull * b->P * Sp * b->ops->input_bytes;
-  HIP_CREATE(hipMalloc(&b->stage_dev, stage));
-  HIP_CREATE(hipHostMalloc(&b->stage_host, stage));
+  RB_TRY(nullptr, b->res.alloc(b->stage_dev, stage));
+  RB_TRY(nullptr, b->res.alloc_host(b->stage_host, stage));
   {
-    void* pc = nullptr;
-    HIP_CREATE(hipHostMalloc(&pc, 16, hipHostMallocMapped | hipHostMallocCoherent));
-    b->pinned_counters = static_cast<volatile uint32_t*>(pc);
+    RB_TRY(nullptr, b->res.alloc_host(b->pinned_counters, 16, hipHostMallocMapped | hipHostMallocCoherent));
     b->pinned_counters[0] = 0;
     void* dp = nullptr;
-    HIP_CREATE(hipHostGetDevicePointer(&dp, pc, 0));
+    RB_TRY(nullptr, hipHostGetDevicePointer(&dp, const_cast<uint32_t*>(b->pinned_counters), 0));
     b->fail_flag_dev = static_cast<uint32_t*>(dp);
   }
-  HIP_CREATE(hipEventCreateWithFlags(&b->stage_ev[0], hipEventDisableTiming));
-  HIP_CREATE(hipEventCreateWithFlags(&b->stage_ev[1], hipEventDisableTiming));
-  HIP_CREATE(hipEventCreateWithFlags(&b->tick_ev, hipEventDisableTiming));
-  HIP_CREATE(hipMemsetAsync(b->snap, 0, W * NW * Gp * 4, b->stream));
-  HIP_CREATE(hipMemsetAsync(b->cs, 0, W * Sp * b->ops->cs_bytes, b->stream));
-  HIP_CREATE(hipMemsetAsync(b->fs, 0, W * Sp * b->ops->cs_bytes, b->stream));
-  HIP_CREATE(hipMemsetAsync(b->ring, 0, kQueueLen * Sp * b->ops->inrec_bytes, b->stream));  // blank inputs
-  HIP_CREATE(hipMemsetAsync(b->last_cs, 0, Sp * b->ops->cs_bytes, b->stream));
-  HIP_CREATE(hipMemsetAsync(b->periodic_cs, 0, Sp * b->ops->cs_bytes, b->stream));
-  HIP_CREATE(hipMemsetAsync(b->err, 0xff, Sp * 4, b->stream));  // NULL_FRAME
-  HIP_CREATE(hipMemsetAsync(b->live_frame, 0xff, Sp * 4, b->stream));
-  HIP_CREATE(hipMemsetAsync(b->frozen, 0, Sp / 64 * 8, b->stream));
-  HIP_CREATE(hipMemsetAsync(b->counters, 0, 16, b->stream));
+  RB_TRY(nullptr, b->res.event(b->stage_ev[0], hipEventDisableTiming));
+  RB_TRY(nullptr, b->res.event(b->stage_ev[1], hipEventDisableTiming));
+  RB_TRY(nullptr, b->res.event(b->tick_ev, hipEventDisableTiming));
+  RB_TRY(nullptr, hipMemsetAsync(b->snap, 0, W * NW * Gp * 4, b->stream));
+  RB_TRY(nullptr, hipMemsetAsync(b->cs, 0, W * Sp * b->ops->cs_bytes, b->stream));
+  RB_TRY(nullptr, hipMemsetAsync(b->fs, 0, W * Sp * b->ops->cs_bytes, b->stream));
+  RB_TRY(nullptr, hipMemsetAsync(b->ring, 0, kQueueLen * Sp * b->ops->inrec_bytes, b->stream));  // blank inputs
+  RB_TRY(nullptr, hipMemsetAsync(b->last_cs, 0, Sp * b->ops->cs_bytes, b->stream));
+  RB_TRY(nullptr, hipMemsetAsync(b->periodic_cs, 0, Sp * b->ops->cs_bytes, b->stream));
+  RB_TRY(nullptr, hipMemsetAsync(b->err, 0xff, Sp * 4, b->stream));  // NULL_FRAME
+  RB_TRY(nullptr, hipMemsetAsync(b->live_frame, 0xff, Sp * 4, b->stream));
+  RB_TRY(nullptr, hipMemsetAsync(b->frozen, 0, Sp / 64 * 8, b->stream));
+  RB_TRY(nullptr, hipMemsetAsync(b->counters, 0, 16, b->stream));
   // State::new for every session (ex_game.rs:234-257), host-evaluated once.
   std::vector<uint32_t> w0(L * NW), planes(NW * Gp);
   b->ops->init_words(w0.data());
   for (size_t s = 0; s < Sp; ++s)
     for (size_t l = 0; l < L; ++l)
       for (size_t k = 0; k < NW; ++k)
-        planes[word_index(static_cast<int>(NW), static_cast<int>(Gp), static_cast<int>(s * L + l), static_cast<int>(k))] =
-            w0[l * NW + k];
-  HIP_CREATE(hipMemcpyAsync(b->live, planes.data(), planes.size() * 4, hipMemcpyHostToDevice, b->stream));
-  HIP_CREATE(hipStreamSynchronize(b->stream));
-#undef HIP_CREATE
+        planes[word_index(static_cast<int>(NW), Gp, s * L + l, static_cast<int>(k))] = w0[l * NW + k];
+  RB_TRY(nullptr, hipMemcpyAsync(b->live, planes.data(), planes.size() * 4, hipMemcpyHostToDevice, b->stream));
+  RB_TRY(nullptr, hipStreamSynchronize(b->stream));
   *out = b.release();
   return RB_OK;
 }
 
-void rb_destroy(rb_batch* b) {
-  if (!b) return;
-  destroy_device(b);
-  delete b;
-}
+void rb_destroy(rb_batch* b) { delete b; }
 
 rb_status rb_set_stream(rb_batch* b, void* s) {
   if (b->plan_only) return RB_OK;
-  HIP_TRY(b, hipStreamSynchronize(b->stream));
+  RB_TRY(b, hipStreamSynchronize(b->stream));
   b->stream = s ? static_cast<hipStream_t>(s) : b->own_stream;
   return RB_OK;
 }
@@ -500,9 +439,9 @@ rb_status rb_add_local_input(rb_batch* b, int32_t handle, const void* inputs, in
   }
   const size_t bytes = static_cast<size_t>(b->S) * b->ops->input_bytes;
   const size_t off = (static_cast<size_t>(b->stage_parity) * b->P + handle) * b->Spad * b->ops->input_bytes;
-  HIP_TRY(b, hipEventSynchronize(b->stage_ev[b->stage_parity]));  // previous copy out of this slot is done
+  RB_TRY(b, hipEventSynchronize(b->stage_ev[b->stage_parity]));  // previous copy out of this slot is done
   std::memcpy(b->stage_host + off, inputs, bytes);
-  HIP_TRY(b, hipMemcpyAsync(b->stage_dev + off, b->stage_host + off, bytes, hipMemcpyHostToDevice, b->stream));
+  RB_TRY(b, hipMemcpyAsync(b->stage_dev + off, b->stage_host + off, bytes, hipMemcpyHostToDevice, b->stream));
   b->in_ptr[handle] = b->stage_dev + off;
   b->staged = true;
   return RB_OK;
@@ -518,9 +457,9 @@ rb_status rb_add_local_inputs_packed(rb_batch* b, const void* inputs, int32_t on
   }
   const size_t bytes = static_cast<size_t>(b->S) * b->P * b->ops->input_bytes;
   const size_t off = static_cast<size_t>(b->stage_parity) * b->P * b->Spad * b->ops->input_bytes;
-  HIP_TRY(b, hipEventSynchronize(b->stage_ev[b->stage_parity]));
+  RB_TRY(b, hipEventSynchronize(b->stage_ev[b->stage_parity]));
   std::memcpy(b->stage_host + off, inputs, bytes);
-  HIP_TRY(b, hipMemcpyAsync(b->stage_dev + off, b->stage_host + off, bytes, hipMemcpyHostToDevice, b->stream));
+  RB_TRY(b, hipMemcpyAsync(b->stage_dev + off, b->stage_host + off, bytes, hipMemcpyHostToDevice, b->stream));
   b->in_ptr[0] = b->stage_dev + off;
   b->staged = true;
   return RB_OK;
@@ -532,7 +471,7 @@ rb_status rb_advance_frame(rb_batch* b) {
   // Checked mode: sessions frozen by the previous tick fail this call
   // (sync_test_session.rs:91-98 returns MismatchedChecksum before any work).
   if (!b->plan_only && (b->cfg.flags & RB_FLAG_CHECKED) && b->tick_pending) {
-    HIP_TRY(b, hipEventSynchronize(b->tick_ev));
+    RB_TRY(b, hipEventSynchronize(b->tick_ev));
     b->tick_pending = false;
     if (b->pinned_counters[0] > 0) result = RB_MISMATCHED_CHECKSUM;
   }
@@ -559,7 +498,7 @@ rb_status rb_advance_frame(rb_batch* b) {
   if (st != RB_OK) return st;
   // the staging slot used by this tick may be refilled once this point passes
   if (b->staged) {
-    HIP_TRY(b, hipEventRecord(b->stage_ev[b->stage_parity], b->stream));
+    RB_TRY(b, hipEventRecord(b->stage_ev[b->stage_parity], b->stream));
     b->stage_parity ^= 1;
     b->staged = false;
   }
@@ -569,7 +508,7 @@ rb_status rb_advance_frame(rb_batch* b) {
   b->display_frame = tp.f0 + tp.n_steps;
   b->tick += 1;
   if (b->cfg.flags & RB_FLAG_CHECKED) {
-    HIP_TRY(b, hipEventRecord(b->tick_ev, b->stream));  // (the kernel sets pinned_counters[0] itself)
+    RB_TRY(b, hipEventRecord(b->tick_ev, b->stream));  // (the kernel sets pinned_counters[0] itself)
     b->tick_pending = true;
   }
   if (result != RB_OK) b->last_err = "Detected checksum mismatch during rollback (see rb_mismatches).";
@@ -622,22 +561,10 @@ rb_status launch_steady_run(rb_batch* b, const uint8_t* tick_inputs, int64_t str
   r.launch_clock = b->clock.next();
   const bool timed = b->prof;
   LaunchEv ev;  // the kernel's own start / end (hipExtLaunchKernel), no marker packets around it
-  if (timed) {
-    if (b->prof_used == b->prof_ev.size()) {
-      hipEvent_t e0 = nullptr, e1 = nullptr;
-      HIP_TRY(b, hipEventCreate(&e0));
-      HIP_TRY(b, hipEventCreate(&e1));
-      b->prof_ev.push_back({e0, e1});
-    }
-    ev = LaunchEv{b->prof_ev[b->prof_used].first, b->prof_ev[b->prof_used].second};
-  }
+  if (timed) RB_TRY(b, b->prof_ev.next(ev));
   hipError_t e = b->ops->launch_steady(r, b->cfg.check_distance, b->block, b->stream, ev);
   if (e != hipSuccess) return fail(b, RB_DEVICE_ERROR, std::string("steady_kernel: ") + hipGetErrorString(e));
-  if (timed) {
-    b->prof_ticks.resize(b->prof_ev.size());
-    b->prof_ticks[b->prof_used] = n;
-    b->prof_used += 1;
-  }
+  if (timed) b->prof_ev.commit(n);
   return RB_OK;
 }
 }  // namespace
@@ -665,15 +592,15 @@ rb_status rb_run_ticks(rb_batch* b, int32_t n_ticks, const void* inputs, int64_t
   void* tmp = nullptr;
   if (!on_device) {
     const size_t tick_bytes = player_bytes * b->P;
-    HIP_TRY(b, hipMallocAsync(&tmp, tick_bytes * n_ticks, b->stream));
-    HIP_TRY(b, hipMemcpy2DAsync(tmp, tick_bytes, inputs, static_cast<size_t>(tick_stride_bytes), tick_bytes, n_ticks,
-                                hipMemcpyHostToDevice, b->stream));
+    RB_TRY(b, hipMallocAsync(&tmp, tick_bytes * n_ticks, b->stream));
+    RB_TRY(b, hipMemcpy2DAsync(tmp, tick_bytes, inputs, static_cast<size_t>(tick_stride_bytes), tick_bytes, n_ticks,
+                               hipMemcpyHostToDevice, b->stream));
     dev_in = static_cast<const uint8_t*>(tmp);
     stride = static_cast<int64_t>(tick_bytes);
   }
   rb_status result = RB_OK;
   if ((b->cfg.flags & RB_FLAG_CHECKED) && b->tick_pending) {
-    HIP_TRY(b, hipEventSynchronize(b->tick_ev));
+    RB_TRY(b, hipEventSynchronize(b->tick_ev));
     b->tick_pending = false;
   }
   const size_t ring_bytes = std::max(static_cast<size_t>(b->W) * b->ops->nw * b->Spad * b->ops->lanes * 4,
@@ -763,7 +690,7 @@ rb_status rb_run_ticks(rb_batch* b, int32_t n_ticks, const void* inputs, int64_t
     // The status waits for the call's launches (the kernels set pinned_counters[0] themselves: nothing
     // is copied).  Measured on the driver's 20-tick call: 86-88 us of wall against 81-83 unchecked;
     // polling a completion event instead took 88-91 (profiles/r06_ab_checked.log).
-    HIP_TRY(b, hipStreamSynchronize(b->stream));
+    RB_TRY(b, hipStreamSynchronize(b->stream));
     if (b->pinned_counters[0] > 0) {
       b->last_err = "Detected checksum mismatch during rollback (see rb_mismatches).";
       result = RB_MISMATCHED_CHECKSUM;
@@ -774,7 +701,7 @@ rb_status rb_run_ticks(rb_batch* b, int32_t n_ticks, const void* inputs, int64_t
 
 rb_status rb_synchronize(rb_batch* b) {
   if (b->plan_only) return RB_OK;
-  HIP_TRY(b, hipStreamSynchronize(b->stream));
+  RB_TRY(b, hipStreamSynchronize(b->stream));
   return RB_OK;
 }
 
@@ -784,8 +711,8 @@ rb_status rb_mismatches(rb_batch* b, int32_t* frames_out, int32_t* count_out) {
     return RB_OK;
   }
   std::vector<int32_t> e(b->Spad);
-  HIP_TRY(b, hipMemcpyAsync(e.data(), b->err, b->Spad * 4, hipMemcpyDeviceToHost, b->stream));
-  HIP_TRY(b, hipStreamSynchronize(b->stream));
+  RB_TRY(b, hipMemcpyAsync(e.data(), b->err, b->Spad * 4, hipMemcpyDeviceToHost, b->stream));
+  RB_TRY(b, hipStreamSynchronize(b->stream));
   int32_t n = 0;
   for (int s = 0; s < b->S; ++s) {
     if (e[s] != kNullFrame) ++n;
@@ -814,12 +741,12 @@ rb_status rb_read_cell(rb_batch* b, int32_t frame, void* images, uint64_t* check
   rb_status st = read_words_slot(b, b->snap + slot * b->ops->nw * b->Spad * b->ops->lanes, planes);
   if (st != RB_OK) return st;
   std::vector<uint8_t> csh(static_cast<size_t>(b->Spad) * b->ops->cs_bytes);
-  HIP_TRY(b, hipMemcpy(csh.data(), static_cast<uint8_t*>(b->cs) + slot * b->Spad * b->ops->cs_bytes, csh.size(),
-                       hipMemcpyDeviceToHost));
+  RB_TRY(b, hipMemcpy(csh.data(), static_cast<uint8_t*>(b->cs) + slot * b->Spad * b->ops->cs_bytes, csh.size(),
+                      hipMemcpyDeviceToHost));
   // A session that stopped on MismatchedChecksum keeps the cells of its last
   // tick: its slot holds the newest frame <= (its final frame - 1) of that slot.
   std::vector<int32_t> stop(static_cast<size_t>(b->Spad));
-  HIP_TRY(b, hipMemcpy(stop.data(), b->live_frame, stop.size() * 4, hipMemcpyDeviceToHost));
+  RB_TRY(b, hipMemcpy(stop.data(), b->live_frame, stop.size() * 4, hipMemcpyDeviceToHost));
   std::vector<uint32_t> w(b->ops->nw * b->ops->lanes);
   for (int s = 0; s < b->S; ++s) {
     words_of(b, planes, s, w.data());
@@ -861,10 +788,10 @@ rb_status rb_read_live(rb_batch* b, void* images, uint64_t* display_checksums, i
   rb_status st = read_words_slot(b, b->live, planes);
   if (st != RB_OK) return st;
   std::vector<uint8_t> dcs(static_cast<size_t>(b->Spad) * b->ops->cs_bytes);
-  HIP_TRY(b, hipMemcpy(dcs.data(), b->last_cs, dcs.size(), hipMemcpyDeviceToHost));
+  RB_TRY(b, hipMemcpy(dcs.data(), b->last_cs, dcs.size(), hipMemcpyDeviceToHost));
   std::vector<int32_t> e(b->Spad), lf(b->Spad);
-  HIP_TRY(b, hipMemcpy(e.data(), b->err, b->Spad * 4, hipMemcpyDeviceToHost));
-  HIP_TRY(b, hipMemcpy(lf.data(), b->live_frame, b->Spad * 4, hipMemcpyDeviceToHost));
+  RB_TRY(b, hipMemcpy(e.data(), b->err, b->Spad * 4, hipMemcpyDeviceToHost));
+  RB_TRY(b, hipMemcpy(lf.data(), b->live_frame, b->Spad * 4, hipMemcpyDeviceToHost));
   std::vector<uint32_t> w(b->ops->nw * b->ops->lanes);
   for (int s = 0; s < b->S; ++s) {
     words_of(b, planes, s, w.data());
@@ -882,8 +809,8 @@ rb_status rb_export_checksum_report(rb_batch* b, int32_t frame, void* dev_out) {
   if (frame < 0 || b->plan->cell_frame[frame % b->W] != frame)
     return fail(b, RB_INVALID_REQUEST, "no cell holds frame " + std::to_string(frame));
   const size_t slot = static_cast<size_t>(frame % b->W);
-  HIP_TRY(b, b->ops->launch_report(static_cast<uint8_t*>(b->cs) + slot * b->Spad * b->ops->cs_bytes, b->err, b->S,
-                                   frame, dev_out, b->stream));
+  RB_TRY(b, b->ops->launch_report(static_cast<uint8_t*>(b->cs) + slot * b->Spad * b->ops->cs_bytes, b->err, b->S,
+                                  frame, dev_out, b->stream));
   return RB_OK;
 }
 
@@ -911,7 +838,7 @@ rb_status rb_export_compact_report(rb_batch* b, int32_t frame, void* dev_out) {
   hipLaunchKernelGGL(rb::compact_report_kernel, dim3((b->S + 255) / 256), dim3(256), 0, b->stream,
                      reinterpret_cast<const uint16_t*>(static_cast<uint8_t*>(b->cs) + slot * b->Spad * 2), b->err, b->S,
                      frame, static_cast<uint32_t*>(dev_out));
-  HIP_TRY(b, hipGetLastError());
+  RB_TRY(b, hipGetLastError());
   return RB_OK;
 }
 
@@ -927,10 +854,10 @@ rb_status rb_debug_corrupt_cell(rb_batch* b, int32_t session, int32_t frame, int
   uint32_t* p = b->snap + static_cast<size_t>(frame % b->W) * b->ops->nw * b->Spad * L +
                 word_index(b->ops->nw, b->Spad * L, session * L + lane, wk);
   uint32_t v;
-  HIP_TRY(b, hipStreamSynchronize(b->stream));
-  HIP_TRY(b, hipMemcpy(&v, p, 4, hipMemcpyDeviceToHost));
+  RB_TRY(b, hipStreamSynchronize(b->stream));
+  RB_TRY(b, hipMemcpy(&v, p, 4, hipMemcpyDeviceToHost));
   v ^= xor_mask;
-  HIP_TRY(b, hipMemcpy(p, &v, 4, hipMemcpyHostToDevice));
+  RB_TRY(b, hipMemcpy(p, &v, 4, hipMemcpyHostToDevice));
   return RB_OK;
 }
 
@@ -940,17 +867,17 @@ rb_status rb_debug_corrupt_cell(rb_batch* b, int32_t session, int32_t frame, int
 template <class Launch>
 static rb_status debug_map2(const char* what, int32_t device, const float* a, const float* b, float* o1, float* o2,
                             int64_t n, Launch launch) {
-  rb_batch* none = nullptr;
   if (n <= 0) return RB_OK;
-  HIP_TRY(none, hipSetDevice(device));
+  RB_TRY(nullptr, hipSetDevice(device));
+  DeviceOwner tmp;  // freed on every return
   float *da = nullptr, *db = nullptr, *d1 = nullptr, *d2 = nullptr;
   uint32_t* du = nullptr;
   const size_t bytes = static_cast<size_t>(n) * 4;
-  hipError_t e = hipMalloc(&da, bytes);
-  if (e == hipSuccess) e = hipMalloc(&db, bytes);
-  if (e == hipSuccess) e = hipMalloc(&d1, bytes);
-  if (e == hipSuccess) e = hipMalloc(&d2, bytes);
-  if (e == hipSuccess) e = hipMalloc(&du, 4);
+  hipError_t e = tmp.alloc(da, bytes);
+  if (e == hipSuccess) e = tmp.alloc(db, bytes);
+  if (e == hipSuccess) e = tmp.alloc(d1, bytes);
+  if (e == hipSuccess) e = tmp.alloc(d2, bytes);
+  if (e == hipSuccess) e = tmp.alloc(du, 4);
   if (e == hipSuccess) e = hipMemset(du, 0, 4);
   if (e == hipSuccess) e = hipMemcpy(da, a, bytes, hipMemcpyHostToDevice);
   if (e == hipSuccess && b) e = hipMemcpy(db, b, bytes, hipMemcpyHostToDevice);
@@ -960,11 +887,6 @@ static rb_status debug_map2(const char* what, int32_t device, const float* a, co
   }
   if (e == hipSuccess) e = hipMemcpy(o1, d1, bytes, hipMemcpyDeviceToHost);
   if (e == hipSuccess) e = hipMemcpy(o2, d2, bytes, hipMemcpyDeviceToHost);
-  (void)hipFree(da);
-  (void)hipFree(db);
-  (void)hipFree(d1);
-  (void)hipFree(d2);
-  (void)hipFree(du);
   if (e != hipSuccess) return fail(nullptr, RB_DEVICE_ERROR, std::string(what) + ": " + hipGetErrorString(e));
   return RB_OK;
 }
@@ -993,9 +915,10 @@ rb_status rb_debug_exgame_inrange(int32_t device, uint32_t first_bits, int64_t n
 rb_status rb_debug_exgame_position_clamp(int32_t device, uint32_t first_bits, int64_t n, uint64_t* diff, float* dev_out) {
   if (n <= 0 || !diff || static_cast<uint64_t>(first_bits) + static_cast<uint64_t>(n) > (1ull << 32)) return RB_INVALID_REQUEST;
   if (hipSetDevice(device) != hipSuccess) return RB_DEVICE_ERROR;
+  DeviceOwner tmp;  // freed on every return
   unsigned long long* d = nullptr;
   const unsigned long long init[2] = {0ull, ~0ull};
-  hipError_t e = hipMalloc(&d, sizeof(init));
+  hipError_t e = tmp.alloc(d, sizeof(init));
   if (e == hipSuccess) e = hipMemcpy(d, init, sizeof(init), hipMemcpyHostToDevice);
   if (e == hipSuccess) {
     hipLaunchKernelGGL(position_clamp_kernel, dim3(static_cast<unsigned>((n + 255) / 256)), dim3(256), 0, nullptr, first_bits,
@@ -1004,7 +927,6 @@ rb_status rb_debug_exgame_position_clamp(int32_t device, uint32_t first_bits, in
   }
   unsigned long long h[2] = {0, 0};
   if (e == hipSuccess) e = hipMemcpy(h, d, sizeof(h), hipMemcpyDeviceToHost);
-  if (d) (void)hipFree(d);
   if (e != hipSuccess) return fail(nullptr, RB_DEVICE_ERROR, std::string("rb_debug_exgame_position_clamp: ") + hipGetErrorString(e));
   diff[0] = h[0];
   diff[1] = h[1];
@@ -1022,58 +944,30 @@ rb_status rb_profile_enable(rb_batch* b, int32_t on) {
   b->prof = on != 0;
   b->prof_every = on > 1 ? static_cast<uint32_t>(on) : 8u;
   b->prof_tick = 0;
-  // Create the event pool now, outside any timed region: a first hipEventCreate
-  // inside one costs tens of microseconds of host time.
   if (b->prof && !b->plan_only) {
-    HIP_TRY(b, hipSetDevice(b->device));
-    const size_t fresh = b->prof_ev.size();
-    while (b->prof_ev.size() < kProfPool) {
-      hipEvent_t e0 = nullptr, e1 = nullptr;
-      HIP_TRY(b, hipEventCreate(&e0));
-      HIP_TRY(b, hipEventCreate(&e1));
-      b->prof_ev.push_back({e0, e1});
-    }
-    // ... and record every new event once: the runtime sets an event's
-    // completion signal up at its first record, which costs host time that
-    // would otherwise land in the first timed call
-    for (size_t i = fresh; i < b->prof_ev.size(); ++i) {
-      HIP_TRY(b, hipEventRecord(b->prof_ev[i].first, b->stream));
-      HIP_TRY(b, hipEventRecord(b->prof_ev[i].second, b->stream));
-    }
-    HIP_TRY(b, hipStreamSynchronize(b->stream));
-    b->prof_ticks.resize(b->prof_ev.size());
+    RB_TRY(b, hipSetDevice(b->device));
+    RB_TRY(b, b->prof_ev.enable(b->stream));
   }
   return RB_OK;
 }
 
 rb_status rb_launch_clock_arm(rb_batch* b, int32_t launches) {
   if (b->plan_only || launches <= 0) return fail(b, RB_INVALID_REQUEST, "rb_launch_clock_arm: plan-only batch or no launches");
-  HIP_TRY(b, hipSetDevice(b->device));
-  HIP_TRY(b, b->clock.arm((static_cast<size_t>(b->Spad) * b->ops->lanes + 63) / 64, static_cast<size_t>(launches), b->stream));
+  RB_TRY(b, hipSetDevice(b->device));
+  // one slot holds every wave of a launch's grid
+  RB_TRY(b, b->clock.arm(b->res, launch_waves(static_cast<size_t>(b->Spad) * b->ops->lanes, b->block), static_cast<size_t>(launches),
+                         b->stream));
   return RB_OK;
 }
 
 rb_status rb_launch_clock_read(rb_batch* b, uint64_t* start_end, int32_t cap, int32_t* launches) {
   if (!b->clock.armed) return fail(b, RB_INVALID_REQUEST, "rb_launch_clock_read: not armed");
-  HIP_TRY(b, b->clock.read(start_end, cap, launches, b->stream));
+  RB_TRY(b, b->clock.read(start_end, cap, launches, b->stream));
   return RB_OK;
 }
 
 rb_status rb_profile_take(rb_batch* b, double* total_ms, int32_t* launches) {
-  double t = 0;
-  int32_t ticks = 0;
-  if (!b->plan_only && b->prof_used > 0) {
-    HIP_TRY(b, hipEventSynchronize(b->prof_ev[b->prof_used - 1].second));
-    for (size_t i = 0; i < b->prof_used; ++i) {
-      float ms = 0;
-      HIP_TRY(b, hipEventElapsedTime(&ms, b->prof_ev[i].first, b->prof_ev[i].second));
-      t += ms;
-      ticks += b->prof_ticks[i];
-    }
-  }
-  if (total_ms) *total_ms = t;
-  if (launches) *launches = ticks;
-  b->prof_used = 0;
+  RB_TRY(b, b->prof_ev.take(total_ms, launches, nullptr));  // the ticks the timed launches covered
   return RB_OK;
 }
 

@@ -29,6 +29,7 @@
 
 #include "../../include/ggrs_amd.h"
 #include "games.hpp"
+#include "host_batch.hpp"
 #include "planner.hpp"
 #include <type_traits>
 #include <utility>
@@ -203,17 +204,7 @@ template <class G>
 constexpr bool steady_saddr() {
   return G::NWL * G::kLanes * 4 <= 80;
 }
-// host mirror of the plane layout
-inline size_t word_index(int NW, int Spad, int s, int k) {
-  const int Q4 = NW / 4, R = NW % 4;
-  if (k < Q4 * 4) return static_cast<size_t>(k / 4) * 4 * Spad + static_cast<size_t>(s) * 4 + (k % 4);
-  size_t b = static_cast<size_t>(Q4) * 4 * Spad;
-  if (R >= 2) {
-    if (k < Q4 * 4 + 2) return b + static_cast<size_t>(s) * 2 + (k - Q4 * 4);
-    b += 2 * static_cast<size_t>(Spad);
-  }
-  return b + s;
-}
+// (the host mirror of the plane layout: session_record.hpp word_index)
 
 // New inputs of this tick.  kPacked: one [S][P] array; else one [S] array per
 // handle.  The host always passes valid pointers (a dummy when there is no new
@@ -857,13 +848,7 @@ __global__ void report_kernel(const typename G::CS* __restrict__ cs, const int32
 #include "spectator.hpp"  // SpectatorSession kernel (likewise)
 namespace rb {
 
-// Kernel timing (rb_profile_enable / rb_p2p_profile_enable): the events a launch
-// records itself through hipExtLaunchKernel — the kernel's own start and end,
-// with no marker packets of their own around it on the stream; both null when
-// the batch is not profiling.
-struct LaunchEv {
-  hipEvent_t start = nullptr, stop = nullptr;
-};
+// A launch that records the events of `ev` itself (host_batch.hpp LaunchEv)
 template <class K, class... A>
 inline hipError_t rb_launch(K kernel, dim3 grid, dim3 block, uint32_t lds, hipStream_t st, const LaunchEv& ev,
                             A... args) {
@@ -874,18 +859,18 @@ inline hipError_t rb_launch(K kernel, dim3 grid, dim3 block, uint32_t lds, hipSt
 
 // rb_launch_clock_arm / rb_p2p_launch_clock_arm: `cap` launch slots of [waves][start, end] words on
 // the device (launch_clock_put), cleared once when armed, so nothing is added to the launches
-// themselves; every launch of the batch takes the next slot until the slots run out.
+// themselves; every launch of the batch takes the next slot until the slots run out.  A slot holds
+// launch_waves() of the batch's widest launch: every wave of a grid stores a start stamp.
 struct LaunchClock {
   unsigned long long* buf = nullptr;
   size_t waves = 0, cap = 0, used = 0, alloc = 0;
   bool armed = false;
-  hipError_t arm(size_t waves_per_launch, size_t launches, hipStream_t st) {
+  hipError_t arm(DeviceOwner& res, size_t waves_per_launch, size_t launches, hipStream_t st) {
     const size_t words = 2 * waves_per_launch * launches;
     if (words > alloc) {
-      if (buf) (void)hipFree(buf);
-      buf = nullptr;
       alloc = 0;
-      hipError_t e = hipMalloc(&buf, words * sizeof(unsigned long long));
+      hipError_t e = res.release(buf);
+      if (e == hipSuccess) e = res.alloc(buf, words * sizeof(unsigned long long));
       if (e != hipSuccess) return e;
       alloc = words;
     }
@@ -917,11 +902,6 @@ struct LaunchClock {
     armed = false;
     used = 0;
     return hipSuccess;
-  }
-  void release() {
-    if (buf) (void)hipFree(buf);
-    buf = nullptr;
-    alloc = 0;
   }
 };
 
@@ -980,13 +960,13 @@ struct GameOpsT final : GameOps {
     return to_u128(reinterpret_cast<const typename G::CS*>(arr)[i]);
   }
   hipError_t launch_tick(const KParams& p, int block, hipStream_t st, const LaunchEv& ev) const override {
-    const int grid = (p.Spad * G::kLanes + block - 1) / block;
+    const int grid = static_cast<int>(launch_grid(p.Spad * G::kLanes, block));
     if (p.in_mode == 2) return rb_launch(tick_kernel<G, true>, dim3(grid), dim3(block), 0, st, ev, p);
     return rb_launch(tick_kernel<G, false>, dim3(grid), dim3(block), 0, st, ev, p);
   }
   template <int CD>
   static hipError_t steady_cd(const RunParams& p, int block, hipStream_t st, const LaunchEv& ev) {
-    const int grid = (p.Spad * G::kLanes + block - 1) / block;
+    const int grid = static_cast<int>(launch_grid(p.Spad * G::kLanes, block));
     if (p.debug) {
 #if RB_EXPERIMENTS
       return rb_launch(steady_kernel<G, CD, true>, dim3(grid), dim3(block), 0, st, ev, p);
@@ -1052,7 +1032,7 @@ struct GameOpsT final : GameOps {
     return k;
   }
   hipError_t launch_p2p(const P2PParams& p, int block, hipStream_t st, const LaunchEv& ev) const override {
-    const int grid = (p.Spad * G::kLanes + block - 1) / block;
+    const int grid = static_cast<int>(launch_grid(p.Spad * G::kLanes, block));
     const P2PLaunchFacts f{p.T, p.W, block, p.packets != nullptr, p.sparse != 0, p.spec_on != 0, p.fan_generic != 0,
                            p.fan_k, p.sync_ticks != 0, p.many_waves != 0, p.tick_log != nullptr, p.ds.interval > 0,
                            p.peer.on != 0};
@@ -1069,7 +1049,7 @@ struct GameOpsT final : GameOps {
   static constexpr bool kFanout = p2p_traits<G>().fanout;
   hipError_t launch_fanout(const FanParams& p, int block, hipStream_t st) const override {
     if constexpr (kFanout) {
-      const int grid = (p.Spad * kSpecBranches * G::kLanes + block - 1) / block;
+      const int grid = static_cast<int>(launch_grid(p.Spad * kSpecBranches * G::kLanes, block));
       hipLaunchKernelGGL(fanout_kernel<G>, dim3(grid), dim3(block), 0, st, p);
       return hipGetLastError();
     } else {
@@ -1077,7 +1057,7 @@ struct GameOpsT final : GameOps {
     }
   }
   hipError_t launch_spectator(const SpectatorParams& p, int block, hipStream_t st) const override {
-    const int grid = (p.Spad * G::kLanes + block - 1) / block;
+    const int grid = static_cast<int>(launch_grid(p.Spad * G::kLanes, block));
     hipLaunchKernelGGL(spectator_kernel<G>, dim3(grid), dim3(block), 0, st, p);
     return hipGetLastError();
   }

@@ -211,4 +211,73 @@ hipError_t move_launch(const PlaneSet& set, const RecordLayout& lay, const int32
 }
 #endif  // RB_RESTART_DEFINE
 
+// ---- The restart and the move of a P2P or a spectator batch B, written once.  B has S, Spad,
+// device, stream, res, tmpl / tmpl_host (the templates of create), restart_idx, move_idx, refused,
+// and says what differs: kApi (the entry points' prefix in messages), planes(ps) (every plane
+// group it has), record_config() (the words its kernels compile in or read: a record goes only
+// into a batch that agrees) and before_move() (the groups a later call would make).
+
+// idx: the selected sessions (empty with a null mask: all of them)
+template <class B>
+rb_status restart_sessions(B* b, const uint8_t* session_mask, std::vector<int32_t>& idx) {
+  if (session_mask) {
+    restart_selected(session_mask, b->S, idx);
+    if (idx.empty()) return RB_OK;
+  }
+  const bool all = !session_mask || idx.size() == static_cast<size_t>(b->S);
+  DeviceScope dev_scope(b->device);
+  PlaneSet ps;
+  ps.Spad = static_cast<size_t>(b->Spad);
+  b->planes(ps);
+  if (ps.tmpl != b->tmpl_host)
+    return fail(b, RB_DEVICE_ERROR, std::string(B::kApi) + "_restart_sessions: the templates moved since create");
+  ps.bind(b->tmpl);
+  if (!all) RB_TRY(b, b->restart_idx.upload(b->res, idx, static_cast<size_t>(b->S), b->stream));
+  RB_TRY(b, restart_launch(ps, all ? nullptr : b->restart_idx.dev, static_cast<uint32_t>(all ? b->S : idx.size()), b->stream));
+  return RB_OK;
+}
+
+// Every per-session plane the batch's configuration can have, the carry-only ones included.
+// layout_only: without making the lazily made groups (their planes have no buffers).
+template <class B>
+RecordLayout record_planes(B* b, PlaneSet& ps, bool layout_only) {
+  ps.Spad = static_cast<size_t>(b->Spad);
+  ps.carry = true;
+  ps.layout_only = layout_only;
+  b->planes(ps);
+  return record_layout(plane_shapes(ps), b->record_config());
+}
+
+template <class B>
+rb_status move_sessions(B* b, const int32_t* sessions, int32_t n, void* records, bool scatter) {
+  const std::string who = std::string(B::kApi) + (scatter ? "_import_sessions" : "_export_sessions");
+  if (n < 0 || (n > 0 && (!sessions || !records))) return fail(b, RB_INVALID_REQUEST, who + ": missing session list or records");
+  if (!move_indices_ok(sessions, n, b->S))
+    return fail(b, RB_INVALID_REQUEST, who + ": sessions must be distinct indices in [0, num_sessions)");
+  if (n == 0) return RB_OK;
+  if (reinterpret_cast<uintptr_t>(records) % 16 != 0) return fail(b, RB_INVALID_REQUEST, who + ": records need 16-byte alignment");
+  DeviceScope dev_scope(b->device);
+  if (const rb_status r = b->before_move(); r != RB_OK) return r;
+  if (scatter && !b->refused) {  // made by the first import
+    RB_TRY(b, b->res.alloc(b->refused, 4));
+    RB_TRY(b, hipMemsetAsync(b->refused, 0, 4, b->stream));
+  }
+  PlaneSet ps;
+  const RecordLayout lay = record_planes(b, ps, false);
+  RB_TRY(b, b->move_idx.upload(b->res, std::vector<int32_t>(sessions, sessions + n), static_cast<size_t>(b->S), b->stream));
+  RB_TRY(b, move_launch(ps, lay, b->move_idx.dev, static_cast<uint32_t>(n), records, scatter, b->refused, b->stream));
+  return RB_OK;
+}
+
+template <class B>
+rb_status import_refused(B* b, uint32_t* count) {
+  if (!count) return RB_OK;
+  *count = 0;
+  if (!b->refused) return RB_OK;  // no import yet
+  DeviceScope dev_scope(b->device);
+  RB_TRY(b, hipMemcpyAsync(count, b->refused, 4, hipMemcpyDeviceToHost, b->stream));
+  RB_TRY(b, hipStreamSynchronize(b->stream));
+  return RB_OK;
+}
+
 }  // namespace rb

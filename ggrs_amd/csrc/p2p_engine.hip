@@ -56,9 +56,9 @@ struct rb_p2p {
   int32_t ts_log_ticks = 0;
   PaceParams pace{};                  // rb_p2p_run_ticks_paced / rb_p2p_pace: the status view, parked ticks, the pacer's accumulator
   bool ticked = false;                // a tick has run (rb_p2p_time_sync_enable comes before the first)
+  DeviceOwner res;                    // every device buffer, pinned buffer and event of the batch
   bool prof = false;
-  std::vector<std::pair<hipEvent_t, hipEvent_t>> prof_ev;
-  size_t prof_used = 0;
+  EventPool prof_ev{res};
   LaunchClock clock;  // rb_p2p_launch_clock_arm
   // the adaptive fan-out (RB_P2P_FLAG_FANOUT without _ALWAYS, include/ggrs_amd.h)
   struct FanPolicy {
@@ -76,72 +76,24 @@ struct rb_p2p {
     int32_t windows = 0, turned_off = 0;
   } fan;
   std::string last_err;
+
+  // what migrate.hpp's restart and move need of a batch
+  static constexpr const char* kApi = "rb_p2p";
+  void planes(PlaneSet& ps);
+  std::vector<uint32_t> record_config() const;
+  rb_status before_move();
+  ~rb_p2p() {
+    if (!own_stream) return;  // nothing was made
+    DeviceScope dev_scope(device);
+    (void)hipStreamSynchronize(stream);
+    res.release_all();
+    (void)hipStreamDestroy(own_stream);
+  }
 };
 constexpr int32_t kFanProbeTicks = 64, kFanPauseTicks = 960;
 constexpr uint64_t kFanMinRollbacks = 64;  // a window with fewer rollbacks decides nothing
 
 namespace {
-thread_local std::string g_p2p_err;
-
-rb_status pfail(rb_p2p* b, rb_status st, const std::string& msg) {
-  if (b) b->last_err = msg;
-  else g_p2p_err = msg;
-  return st;
-}
-#define P2P_TRY(b, expr)                                                                                    \
-  do {                                                                                                      \
-    hipError_t _e = (expr);                                                                                 \
-    if (_e != hipSuccess) return pfail((b), RB_DEVICE_ERROR, std::string(#expr ": ") + hipGetErrorString(_e)); \
-  } while (0)
-
-void free_all(rb_p2p* b) {
-  (void)hipSetDevice(b->device);
-  if (b->stream) (void)hipStreamSynchronize(b->stream);
-  void* ptrs[] = {b->snap,   b->cs,      b->tag,       b->ring,       b->live,    b->qs,       b->status,
-                  b->trace,  b->counters, b->stats, b->spec_state, b->spec_cells, b->spec_cs, b->spec_meta,
-                  b->disc_mask, b->tmpl};
-  for (void* q : ptrs)
-    if (q) (void)hipFree(q);
-  void* dptrs[] = {b->ds.lh_frame, b->ds.lh_cs,    b->ds.rh_frame, b->ds.rh_lo,     b->ds.rh_hi,
-                   b->ds.rh_meta,  b->ds.ob_frame, b->ds.ob_cs,    b->ds.ob_n,      b->ds.ev_n,
-                   b->ds.ev_frame, b->ds.ev_handle, b->ds.ev_local, b->ds.ev_remote};
-  for (void* q : dptrs)
-    if (q) (void)hipFree(q);
-  b->restart_idx.release();
-  b->move_idx.release();
-  if (b->refused) (void)hipFree(b->refused);
-  if (b->fan.dev) (void)hipFree(b->fan.dev);
-  if (b->fan.host) (void)hipHostFree(b->fan.host);
-  if (b->fan.ev) (void)hipEventDestroy(b->fan.ev);
-  if (b->peer.last) (void)hipFree(b->peer.last);
-  if (b->peer.disc) (void)hipFree(b->peer.disc);
-  if (b->exp_state) (void)hipFree(b->exp_state);
-  if (b->ts.state) (void)hipFree(b->ts.state);
-  if (b->ts.win) (void)hipFree(b->ts.win);
-  if (b->ts_log) (void)hipFree(b->ts_log);
-  if (b->pace.view) (void)hipFree(b->pace.view);
-  if (b->pace.parked) (void)hipFree(b->pace.parked);
-  if (b->pace.acc) (void)hipFree(b->pace.acc);
-  for (auto& pr : b->prof_ev) {
-    (void)hipEventDestroy(pr.first);
-    (void)hipEventDestroy(pr.second);
-  }
-  b->clock.release();
-  if (b->own_stream) (void)hipStreamDestroy(b->own_stream);
-}
-
-template <class T>
-rb_status read_rows(rb_p2p* b, const T* dev, size_t rows, std::vector<T>& host) {
-  host.resize(rows * static_cast<size_t>(b->Spad));
-  P2P_TRY(b, hipMemcpyAsync(host.data(), dev, host.size() * sizeof(T), hipMemcpyDeviceToHost, b->stream));
-  P2P_TRY(b, hipStreamSynchronize(b->stream));
-  return RB_OK;
-}
-
-// session s's words [lanes][nw] from a block of lane planes, as its canonical image
-// disconnect_player_at_frame (p2p_session.rs:555-581) for one remote handle:
-// mark it disconnected and, if the session already simulated past its last
-// input, set disconnect_frame = last_frame + 1
 // The adaptive fan-out's measurement: selects and LoadGameStates summed over the batch into out[0..1].
 __global__ void fan_sums_kernel(const unsigned long long* __restrict__ stats, int S, int Spad,
                                 unsigned long long* __restrict__ out) {
@@ -286,23 +238,24 @@ __global__ void p2p_export_kernel(const int32_t* __restrict__ qs, const uint8_t*
   }
 }
 
+// session s's words [lanes][nw] from a block of lane planes, as its canonical image
 void image_from_planes(const rb_p2p* b, const std::vector<uint32_t>& planes, int s, int32_t frame, uint8_t* out) {
-  const int L = b->ops->lanes, NW = b->ops->nw;
-  std::vector<uint32_t> w(static_cast<size_t>(L) * NW);
-  for (int l = 0; l < L; ++l)
-    for (int k = 0; k < NW; ++k) w[l * NW + k] = planes[word_index(NW, b->Spad * L, s * L + l, k)];
+  std::vector<uint32_t> w(static_cast<size_t>(b->ops->lanes) * b->ops->nw);
+  session_words(planes.data(), b->ops->nw, b->ops->lanes, b->Spad, s, w.data());
   b->ops->image(w.data(), frame, out);
 }
 }  // namespace
 
 namespace {
-// ---- What a fresh session holds, one function per buffer group (restart.hpp).  The call that makes
-// a group's buffers writes these values into every column, rb_p2p_restart_sessions into the selected
-// sessions' columns: the values stand here and nowhere else.  A group whose buffers do not exist
-// adds nothing.  Batch-wide buffers (counters, stats, the fan-out's sums) are not per session.
+// ---- What a fresh session holds and the extent of each per-session buffer, one function per
+// buffer group (restart.hpp).  The call that makes a group (make_group; create for the first four)
+// allocates its buffers from these shapes and writes these values into every column,
+// rb_p2p_restart_sessions into the selected sessions' columns: sizes and values stand here and
+// nowhere else.  A group the batch does not have adds nothing.  Batch-wide buffers (counters,
+// stats, the fan-out's sums) are not per session.
 
 // SyncLayer::new, InputQueue::new and ConnectionStatus::default for every handle, no tick yet
-void core_planes(const rb_p2p* b, PlaneSet& ps) {
+void core_planes(rb_p2p* b, PlaneSet& ps) {
   const int NW = b->ops->nw, L = b->ops->lanes;
   std::vector<uint32_t> w0(static_cast<size_t>(L) * NW);
   b->ops->init_words(w0.data());
@@ -329,21 +282,27 @@ void core_planes(const rb_p2p* b, PlaneSet& ps) {
 // behind a valid row, and a row is valid only for the tick after the launch that made it, unless
 // the batch's adaptive policy has cleared it (fan_invalidate): batch-wide.  So a move carries
 // neither: an imported session has no valid branch, as a restarted one.
-void fanout_planes(const rb_p2p* b, PlaneSet& ps) {
-  if (!b->spec_meta) return;
+void fanout_planes(rb_p2p* b, PlaneSet& ps) {
+  if (!b->fanout) return;
+  // branch columns per lane column: 16 (fanout_kernel: [session][branch][lane]; the one-player in-kernel
+  // fan-out uses 16 + L of 16 * L), plus one own chain per lane for the per-player form
+  const size_t K = kSpecBranches + (b->per_player ? 1 : 0), NW = b->ops->nw, W = b->W;
+  ps.buffer(b->spec_state, 4, K * NW, b->ops->lanes);
+  ps.buffer(b->spec_cells, 4, W * K * NW, b->ops->lanes);
+  ps.buffer(b->spec_cs, b->ops->cs_bytes, W * K, 1);
   ps.fill(b->spec_meta, 4, SM_COUNT, 1, 0);
   ps.fresh_on_move();
 }
 // ConnectionStatus::default for every (endpoint, player)
-void peer_planes(const rb_p2p* b, PlaneSet& ps) {
-  if (!b->peer.last) return;
+void peer_planes(rb_p2p* b, PlaneSet& ps) {
+  if (!b->peer.on) return;
   ps.fill(b->peer.last, 4, 16, 1, 0xff);  // NULL_FRAME
   ps.fill(b->peer.disc, 4, 16, 1, 0);
 }
 // empty histories, outbox and event rings (entries behind a count or a NULL frame are never read)
-void desync_planes(const rb_p2p* b, PlaneSet& ps) {
-  const DesyncParams& d = b->ds;
-  if (!d.lh_frame) return;
+void desync_planes(rb_p2p* b, PlaneSet& ps) {
+  DesyncParams& d = b->ds;
+  if (d.interval <= 0) return;
   ps.fill(d.lh_frame, 4, kCsHist, 1, 0xff);  // NULL_FRAME: empty slot
   ps.fill(d.lh_cs, 8, kCsHist, 1, 0);
   ps.fill(d.rh_frame, 4, 4 * kCsHist, 1, 0xff);
@@ -361,66 +320,57 @@ void desync_planes(const rb_p2p* b, PlaneSet& ps) {
   ps.carried(d.ev_remote, 8, kEvents, 1);
 }
 // next_spectator_frame = 0 (p2p_session.rs:201), status RB_P2P_EXPORT_OK
-void export_planes(const rb_p2p* b, PlaneSet& ps) {
-  if (b->exp_state || ps.layout_only) ps.fill(b->exp_state, 4, 2, 1, 0);
+void export_planes(rb_p2p* b, PlaneSet& ps) {
+  if (b->exp_state || ps.make || ps.layout_only) ps.fill(b->exp_state, 4, 2, 1, 0);
 }
 // TimeSync::default, local / remote_frame_advantage 0, round_trip_time 0, next_recommended_sleep 0,
 // frames_ahead 0, no event
-void time_sync_planes(const rb_p2p* b, PlaneSet& ps) {
-  if (!b->ts.state) return;
+void time_sync_planes(rb_p2p* b, PlaneSet& ps) {
+  if (!b->ts_on && !ps.make) return;
   ps.fill(b->ts.state, 4, TS_ROWS, 1, 0);
   ps.fill(b->ts.win, 4, 2 * static_cast<size_t>(kTsWindow) * 4, 1, 0);
 }
 // nothing parked yet, acc = 0
-void pace_planes(const rb_p2p* b, PlaneSet& ps) {
-  if (!b->pace.view && !(ps.layout_only && !b->fanout)) return;  // a fan-out batch never paces
+void pace_planes(rb_p2p* b, PlaneSet& ps) {
+  if (!b->pace.view && !ps.make && !(ps.layout_only && !b->fanout)) return;  // a fan-out batch never paces
   ps.fill(b->pace.view, 4, 1, 1, 0);
   ps.fill(b->pace.parked, 4, 1, 1, 0);
   ps.fill(b->pace.acc, 4, 1, 1, 0);
 }
-// every group the batch has, the groups with templates first (their offsets are those of create)
-void all_planes(const rb_p2p* b, PlaneSet& ps) {
-  ps.Spad = static_cast<size_t>(b->Spad);
+// the groups create makes, the groups with templates first (their offsets are those of create)
+void create_planes(rb_p2p* b, PlaneSet& ps) {
   core_planes(b, ps);
   desync_planes(b, ps);
   fanout_planes(b, ps);
   peer_planes(b, ps);
-  export_planes(b, ps);
-  time_sync_planes(b, ps);
-  pace_planes(b, ps);
 }
-// a freshly made group's values into every column, padding included
-hipError_t fill_group(const rb_p2p* b, void (*group)(const rb_p2p*, PlaneSet&)) {
+// Make a group: its buffers that do not exist yet, then its fresh values into every column, padding included.
+rb_status make_group(rb_p2p* b, void (*group)(rb_p2p*, PlaneSet&)) {
   PlaneSet ps;
   ps.Spad = static_cast<size_t>(b->Spad);
+  ps.make = &b->res;
   group(b, ps);
+  RB_TRY(b, ps.err);
   ps.bind(b->tmpl);
-  return restart_launch(ps, nullptr, static_cast<uint32_t>(b->Spad), b->stream);
-}
-
-// The pacing buffers, made by the first call that needs them.
-rb_status pace_reserve(rb_p2p* b) {
-  if (b->pace.view) return RB_OK;
-  const size_t bytes = static_cast<size_t>(b->Spad) * 4;
-  P2P_TRY(b, hipMalloc(&b->pace.view, bytes));
-  P2P_TRY(b, hipMalloc(&b->pace.parked, bytes));
-  P2P_TRY(b, hipMalloc(&b->pace.acc, bytes));
-  P2P_TRY(b, fill_group(b, pace_planes));
+  RB_TRY(b, restart_launch(ps, nullptr, static_cast<uint32_t>(b->Spad), b->stream));
   return RB_OK;
 }
-// The export's rows, made by the first call that needs them.
-rb_status export_reserve(rb_p2p* b) {
-  if (b->exp_state) return RB_OK;
-  P2P_TRY(b, hipMalloc(&b->exp_state, 2 * static_cast<size_t>(b->Spad) * 4));
-  P2P_TRY(b, fill_group(b, export_planes));
-  return RB_OK;
-}
+// The pacing buffers and the export's rows, made by the first call that needs them.
+rb_status pace_reserve(rb_p2p* b) { return b->pace.view ? RB_OK : make_group(b, pace_planes); }
+rb_status export_reserve(rb_p2p* b) { return b->exp_state ? RB_OK : make_group(b, export_planes); }
 template <int IB>
 auto poll_kernel_of(int P) {
   return P == 1 ? p2p_poll_kernel<IB, 1> : P == 2 ? p2p_poll_kernel<IB, 2> : P == 3 ? p2p_poll_kernel<IB, 3> : p2p_poll_kernel<IB, 4>;
 }
 }  // namespace
 
+// every group the batch has
+void rb_p2p::planes(PlaneSet& ps) {
+  create_planes(this, ps);
+  export_planes(this, ps);
+  time_sync_planes(this, ps);
+  pace_planes(this, ps);
+}
 
 extern "C" {
 
@@ -439,51 +389,51 @@ void rb_p2p_config_init(rb_p2p_config* c) {
   c->fanout_candidates = kSpecBranches;
 }
 
-const char* rb_p2p_last_error(const rb_p2p* b) { return b ? b->last_err.c_str() : g_p2p_err.c_str(); }
+const char* rb_p2p_last_error(const rb_p2p* b) { return b ? b->last_err.c_str() : g_create_err.c_str(); }
 
 rb_status rb_p2p_create(const rb_p2p_config* cfg, rb_p2p** out) {
   *out = nullptr;
-  if (!cfg || cfg->abi_version != RB_ABI_VERSION) return pfail(nullptr, RB_INVALID_REQUEST, "rb_p2p_config.abi_version mismatch");
+  if (!cfg || cfg->abi_version != RB_ABI_VERSION) return fail(nullptr, RB_INVALID_REQUEST, "rb_p2p_config.abi_version mismatch");
   if (cfg->max_prediction <= 0)  // builder.rs:136-145
-    return pfail(nullptr, RB_INVALID_REQUEST, "Currently, only prediction windows above 0 are supported");
+    return fail(nullptr, RB_INVALID_REQUEST, "Currently, only prediction windows above 0 are supported");
   if (cfg->num_players <= 0 || cfg->num_players > 4 || cfg->num_sessions <= 0 || cfg->input_delay < 0 ||
       cfg->remote_delay < 0 || cfg->desync_interval < 0)
-    return pfail(nullptr, RB_INVALID_REQUEST, "num_players must be 1..4; sizes and delays non-negative");
+    return fail(nullptr, RB_INVALID_REQUEST, "num_players must be 1..4; sizes and delays non-negative");
   const uint32_t all = (1u << cfg->num_players) - 1u;
   if ((cfg->local_mask & ~all) != 0)  // builder.rs:103-115: handles must be < num_players
-    return pfail(nullptr, RB_INVALID_REQUEST,
-                 "The player handle you provided is invalid. For a local player, the handle should be between 0 and num_players");
+    return fail(nullptr, RB_INVALID_REQUEST,
+                "The player handle you provided is invalid. For a local player, the handle should be between 0 and num_players");
   if (cfg->local_mask == 0 || cfg->local_mask == all)
-    return pfail(nullptr, RB_INVALID_REQUEST, "a P2P batch needs at least one local and one remote handle");
+    return fail(nullptr, RB_INVALID_REQUEST, "a P2P batch needs at least one local and one remote handle");
   if (cfg->max_prediction > 64 || cfg->input_delay + cfg->max_prediction + 2 > kQueueLen)
-    return pfail(nullptr, RB_INVALID_REQUEST, "max_prediction / input delay do not fit the 128-entry input queue");
+    return fail(nullptr, RB_INVALID_REQUEST, "max_prediction / input delay do not fit the 128-entry input queue");
   if (cfg->game != RB_GAME_EX_GAME && cfg->game != RB_GAME_STUB && cfg->game != RB_GAME_STUB_ENUM &&
       cfg->game != RB_GAME_BRAWLER && cfg->game < RB_GAME_PLUGIN_BASE)
-    return pfail(nullptr, RB_INVALID_REQUEST,
-                 "P2P batches support ex_game, the stub games, the brawler and registered plugin games");
+    return fail(nullptr, RB_INVALID_REQUEST,
+                "P2P batches support ex_game, the stub games, the brawler and registered plugin games");
   auto ops = make_game(cfg->game, cfg->num_players, (cfg->flags & RB_FLAG_LANE_PER_SESSION) != 0);
-  if (!ops) return pfail(nullptr, RB_INVALID_REQUEST, "unsupported game / num_players combination (RB_FLAG_LANE_PER_SESSION: A/B builds only)");
+  if (!ops) return fail(nullptr, RB_INVALID_REQUEST, "unsupported game / num_players combination (RB_FLAG_LANE_PER_SESSION: A/B builds only)");
   const bool fanout = (cfg->flags & RB_P2P_FLAG_FANOUT) != 0;
   if (fanout && (!ops->fanout_supported || cfg->sparse_saving))
-    return pfail(nullptr, RB_INVALID_REQUEST,
-                 "speculative fan-out needs ex_game with one lane per player or the brawler, no sparse saving");
+    return fail(nullptr, RB_INVALID_REQUEST,
+                "speculative fan-out needs ex_game with one lane per player or the brawler, no sparse saving");
   if (fanout && (cfg->fanout_candidates < 1 || cfg->fanout_candidates > kSpecBranches))
-    return pfail(nullptr, RB_INVALID_REQUEST, "fanout_candidates must be 1..16");
+    return fail(nullptr, RB_INVALID_REQUEST, "fanout_candidates must be 1..16");
   const bool per_player = fanout && (cfg->flags & RB_P2P_FLAG_FANOUT_PER_PLAYER) != 0;
   if (per_player && (!ops->inlane_fanout || ops->input_alphabet > static_cast<uint32_t>(cfg->fanout_candidates)))
-    return pfail(nullptr, RB_INVALID_REQUEST,
-                 "per-player speculation needs independent players (ex_game) and fanout_candidates covering the "
-                 "input alphabet");
+    return fail(nullptr, RB_INVALID_REQUEST,
+                "per-player speculation needs independent players (ex_game) and fanout_candidates covering the "
+                "input alphabet");
   if (static_cast<uint64_t>(cfg->max_prediction) * ops->nw * ops->lanes *
           ((static_cast<uint64_t>(cfg->num_sessions) + 63) / 64 * 64) >= (1ull << 32))
-    return pfail(nullptr, RB_INVALID_REQUEST, "batch too large for 32-bit snapshot offsets");
+    return fail(nullptr, RB_INVALID_REQUEST, "batch too large for 32-bit snapshot offsets");
   // the fan-out's branch planes: a slot's offset is 64-bit (p2p.hpp), the words inside one slot
   // (planes x columns, load_words / store_words) are int offsets: at most 2^31 words per slot (the
   // brawler at 65,536 sessions is exactly that: 32 planes of 2^26 columns, the last plane's int
   // offset 31 x 2^26)
   if (fanout && static_cast<uint64_t>(ops->nw) * ops->lanes * (kSpecBranches + (per_player ? 1 : 0)) *
                         ((static_cast<uint64_t>(cfg->num_sessions) + 63) / 64 * 64) > (1ull << 31))
-    return pfail(nullptr, RB_INVALID_REQUEST, "batch too large for the fan-out's 31-bit branch-plane offsets");
+    return fail(nullptr, RB_INVALID_REQUEST, "batch too large for the fan-out's 31-bit branch-plane offsets");
 
   auto b = std::make_unique<rb_p2p>();
   b->cfg = *cfg;
@@ -493,109 +443,57 @@ rb_status rb_p2p_create(const rb_p2p_config* cfg, rb_p2p** out) {
   b->W = cfg->max_prediction;
   b->P = cfg->num_players;
   b->block = cfg->block_size ? static_cast<int>(cfg->block_size) : 256;
-  if (b->block % 64 != 0 || b->block > 256) return pfail(nullptr, RB_INVALID_REQUEST, "block_size must be 64, 128, 192 or 256");
+  if (b->block % 64 != 0 || b->block > 256) return fail(nullptr, RB_INVALID_REQUEST, "block_size must be 64, 128, 192 or 256");
   b->device = cfg->device;
   b->fanout = fanout;
   b->per_player = per_player;
   if (const char* e = std::getenv("RB_P2P_SYNC_TICKS")) b->sync_ticks = std::atoi(e) != 0;
   if (const char* e = std::getenv("RB_FANOUT_GENERIC")) b->fan_generic = std::atoi(e) != 0;
-  rb_p2p* bp = b.get();
-  auto hip_fail = [&](hipError_t e, const char* what) {
-    g_p2p_err = std::string(what) + ": " + hipGetErrorString(e);
-    free_all(bp);
-    return RB_DEVICE_ERROR;
-  };
-#define P2P_CREATE(expr)                              \
-  do {                                                \
-    hipError_t _e = (expr);                           \
-    if (_e != hipSuccess) return hip_fail(_e, #expr); \
-  } while (0)
-  P2P_CREATE(hipSetDevice(b->device));
-  int cus = 0;
-  P2P_CREATE(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, b->device));
-  b->simds = 4 * cus;  // 4 SIMDs per CU (CDNA)
-  P2P_CREATE(hipStreamCreateWithFlags(&b->own_stream, hipStreamNonBlocking));
-  b->stream = b->own_stream;
-  const size_t Sp = b->Spad, NW = b->ops->nw, W = b->W, L = b->ops->lanes, Gp = Sp * L;
-  const size_t ring_bytes = static_cast<size_t>(kQueueLen) * b->P * Sp * b->ops->input_bytes;
-  P2P_CREATE(hipMalloc(&b->snap, W * NW * Gp * 4));
-  P2P_CREATE(hipMalloc(&b->cs, W * Sp * b->ops->cs_bytes));
-  P2P_CREATE(hipMalloc(&b->tag, W * Sp * 4));
-  P2P_CREATE(hipMalloc(&b->ring, ring_bytes));
-  P2P_CREATE(hipMalloc(&b->live, NW * Gp * 4));
-  P2P_CREATE(hipMalloc(&b->qs, kQsFields * Sp * 4));
-  P2P_CREATE(hipMalloc(&b->status, Sp * 4));
-  P2P_CREATE(hipMalloc(&b->trace, Sp * 4));
-  P2P_CREATE(hipMalloc(&b->counters, 16));
-  P2P_CREATE(hipMalloc(&b->stats, ST_COUNT * Sp * 8));
-  // the per-session buffers are filled below, from the plane groups
-  P2P_CREATE(hipMemsetAsync(b->counters, 0, 16, b->stream));
-  P2P_CREATE(hipMemsetAsync(b->stats, 0, ST_COUNT * Sp * 8, b->stream));
-  if (b->fanout) {
-    // branch columns per lane column: 16 (fanout_kernel: [session][branch][lane]; the one-player in-kernel
-    // fan-out uses 16 + L of 16 * L), plus one own chain per lane for the per-player form
-    const size_t K = kSpecBranches + (per_player ? 1 : 0);
-    P2P_CREATE(hipMalloc(&b->spec_state, K * NW * Gp * 4));
-    P2P_CREATE(hipMalloc(&b->spec_cells, W * K * NW * Gp * 4));
-    P2P_CREATE(hipMalloc(&b->spec_cs, W * K * Sp * b->ops->cs_bytes));
-    P2P_CREATE(hipMalloc(&b->spec_meta, SM_COUNT * Sp * 4));
-    b->fan.adaptive = (cfg->flags & RB_P2P_FLAG_FANOUT_ALWAYS) == 0;
-    if (cfg->fanout_min_select_permille) b->fan.min_permille = cfg->fanout_min_select_permille;
-    if (b->fan.adaptive) {
-      P2P_CREATE(hipMalloc(&b->fan.dev, 4 * sizeof(unsigned long long)));
-      P2P_CREATE(hipHostMalloc(&b->fan.host, 4 * sizeof(unsigned long long)));
-      P2P_CREATE(hipEventCreateWithFlags(&b->fan.ev, hipEventDisableTiming));
-    }
-  }
+  b->fan.adaptive = fanout && (cfg->flags & RB_P2P_FLAG_FANOUT_ALWAYS) == 0;
+  if (cfg->fanout_min_select_permille) b->fan.min_permille = cfg->fanout_min_select_permille;
+  b->peer.on = (cfg->flags & RB_P2P_FLAG_PEER_STATUS) ? 1 : 0;
+  b->ds.interval = cfg->desync_interval;
   b->disconnected.assign(static_cast<size_t>(b->P) * b->S, 0);
-  P2P_CREATE(hipMalloc(&b->disc_mask, Sp));
-  if (cfg->flags & RB_P2P_FLAG_PEER_STATUS) {
-    P2P_CREATE(hipMalloc(&b->peer.last, 16 * Sp * 4));
-    P2P_CREATE(hipMalloc(&b->peer.disc, 16 * Sp * 4));
-    b->peer.on = 1;
+  // a failure from here on frees what was made (~rb_p2p) and leaves its message for rb_p2p_last_error(nullptr)
+  DeviceScope dev_scope(b->device);
+  int cus = 0;
+  RB_TRY(nullptr, hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, b->device));
+  b->simds = 4 * cus;  // 4 SIMDs per CU (CDNA)
+  RB_TRY(nullptr, hipStreamCreateWithFlags(&b->own_stream, hipStreamNonBlocking));
+  b->stream = b->own_stream;
+  // the batch-wide buffers
+  const size_t Sp = b->Spad;
+  RB_TRY(nullptr, b->res.alloc(b->counters, 16));
+  RB_TRY(nullptr, b->res.alloc(b->stats, ST_COUNT * Sp * 8));
+  RB_TRY(nullptr, hipMemsetAsync(b->counters, 0, 16, b->stream));
+  RB_TRY(nullptr, hipMemsetAsync(b->stats, 0, ST_COUNT * Sp * 8, b->stream));
+  RB_TRY(nullptr, b->res.alloc(b->disc_mask, Sp));
+  if (b->fan.adaptive) {
+    RB_TRY(nullptr, b->res.alloc(b->fan.dev, 4 * sizeof(unsigned long long)));
+    RB_TRY(nullptr, b->res.alloc_host(b->fan.host, 4 * sizeof(unsigned long long)));
+    RB_TRY(nullptr, b->res.event(b->fan.ev, hipEventDisableTiming));
   }
-  if (cfg->desync_interval > 0) {
-    DesyncParams& d = b->ds;
-    d.interval = cfg->desync_interval;
-    const size_t H = kCsHist, R = 4;
-    P2P_CREATE(hipMalloc(&d.lh_frame, H * Sp * 4));
-    P2P_CREATE(hipMalloc(&d.lh_cs, H * Sp * 8));
-    P2P_CREATE(hipMalloc(&d.rh_frame, R * H * Sp * 4));
-    P2P_CREATE(hipMalloc(&d.rh_lo, R * H * Sp * 8));
-    P2P_CREATE(hipMalloc(&d.rh_hi, R * H * Sp * 8));
-    P2P_CREATE(hipMalloc(&d.rh_meta, R * 3 * Sp * 4));
-    P2P_CREATE(hipMalloc(&d.ob_frame, kOutbox * Sp * 4));
-    P2P_CREATE(hipMalloc(&d.ob_cs, kOutbox * Sp * 8));
-    P2P_CREATE(hipMalloc(&d.ob_n, Sp * 4));
-    P2P_CREATE(hipMalloc(&d.ev_n, Sp * 4));
-    P2P_CREATE(hipMalloc(&d.ev_frame, kEvents * Sp * 4));
-    P2P_CREATE(hipMalloc(&d.ev_handle, kEvents * Sp * 4));
-    P2P_CREATE(hipMalloc(&d.ev_local, kEvents * Sp * 8));
-    P2P_CREATE(hipMalloc(&d.ev_remote, kEvents * Sp * 8));
-  }
-  // every session fresh: the plane groups' values into every column, their templates kept on the
-  // device for rb_p2p_restart_sessions
+  // every session fresh: the plane groups' buffers made, their values into every column, their
+  // templates kept on the device for rb_p2p_restart_sessions
   PlaneSet ps;
-  all_planes(bp, ps);
+  ps.Spad = Sp;
+  ps.make = &b->res;
+  create_planes(b.get(), ps);
+  RB_TRY(nullptr, ps.err);
   b->tmpl_host = ps.tmpl;
-  P2P_CREATE(hipMalloc(&b->tmpl, ps.tmpl.size() * 4));
-  P2P_CREATE(hipMemcpyAsync(b->tmpl, ps.tmpl.data(), ps.tmpl.size() * 4, hipMemcpyHostToDevice, b->stream));
+  RB_TRY(nullptr, b->res.alloc(b->tmpl, ps.tmpl.size() * 4));
+  RB_TRY(nullptr, hipMemcpyAsync(b->tmpl, ps.tmpl.data(), ps.tmpl.size() * 4, hipMemcpyHostToDevice, b->stream));
   ps.bind(b->tmpl);
-  P2P_CREATE(restart_launch(ps, nullptr, static_cast<uint32_t>(b->Spad), b->stream));
-  P2P_CREATE(hipStreamSynchronize(b->stream));
-#undef P2P_CREATE
+  RB_TRY(nullptr, restart_launch(ps, nullptr, static_cast<uint32_t>(b->Spad), b->stream));
+  RB_TRY(nullptr, hipStreamSynchronize(b->stream));
   *out = b.release();
   return RB_OK;
 }
 
-void rb_p2p_destroy(rb_p2p* b) {
-  if (!b) return;
-  free_all(b);
-  delete b;
-}
+void rb_p2p_destroy(rb_p2p* b) { delete b; }
 
 rb_status rb_p2p_set_stream(rb_p2p* b, void* s) {
-  P2P_TRY(b, hipStreamSynchronize(b->stream));
+  RB_TRY(b, hipStreamSynchronize(b->stream));
   b->stream = s ? static_cast<hipStream_t>(s) : b->own_stream;
   return RB_OK;
 }
@@ -640,6 +538,28 @@ P2PParams base_params(const rb_p2p* b) {
   p.peer = b->peer;
   return p;
 }
+// ... and for a fanout_kernel launch
+FanParams fan_params(const rb_p2p* b) {
+  FanParams fp{};
+  fp.status = b->status;
+  fp.snap = b->snap;
+  fp.tag = b->tag;
+  fp.ring = b->ring;
+  fp.qs = b->qs;
+  fp.spec_state = b->spec_state;
+  fp.spec_cells = b->spec_cells;
+  fp.spec_cs = b->spec_cs;
+  fp.spec_meta = b->spec_meta;
+  fp.stats = b->stats;
+  fp.counters = b->counters;
+  fp.S = b->S;
+  fp.Spad = b->Spad;
+  fp.W = b->W;
+  fp.local_mask = b->cfg.local_mask;
+  fp.fan_generic = b->fan_generic ? 1 : 0;
+  fp.fan_k = b->cfg.fanout_candidates;
+  return fp;
+}
 }  // namespace
 
 namespace {
@@ -651,27 +571,27 @@ namespace {
 // speculates depends only on the batch's inputs and call sizes, never on when a copy landed.
 constexpr int32_t kFanDecideTicks = 16;
 rb_status fan_snapshot(rb_p2p* b, int off) {
-  P2P_TRY(b, hipMemsetAsync(b->fan.dev + off, 0, 2 * sizeof(unsigned long long), b->stream));
+  RB_TRY(b, hipMemsetAsync(b->fan.dev + off, 0, 2 * sizeof(unsigned long long), b->stream));
   hipLaunchKernelGGL(fan_sums_kernel, dim3((b->S + 255) / 256), dim3(256), 0, b->stream, b->stats, b->S, b->Spad,
                      b->fan.dev + off);
-  P2P_TRY(b, hipGetLastError());
-  P2P_TRY(b, hipMemcpyAsync(b->fan.host + off, b->fan.dev + off, 2 * sizeof(unsigned long long),
-                            hipMemcpyDeviceToHost, b->stream));
+  RB_TRY(b, hipGetLastError());
+  RB_TRY(b, hipMemcpyAsync(b->fan.host + off, b->fan.dev + off, 2 * sizeof(unsigned long long),
+                           hipMemcpyDeviceToHost, b->stream));
   return RB_OK;
 }
 // Branches are valid only for the tick right after the launch that made them (SM_END == current
 // frame); a pause's plain ticks leave the metadata as it was, so it is cleared when presimulation
 // stops and again when it restarts.
 rb_status fan_invalidate(rb_p2p* b) {
-  P2P_TRY(b, hipMemsetAsync(b->spec_meta + static_cast<size_t>(SM_VALID) * b->Spad, 0, static_cast<size_t>(b->Spad) * 4,
-                            b->stream));
+  RB_TRY(b, hipMemsetAsync(b->spec_meta + static_cast<size_t>(SM_VALID) * b->Spad, 0, static_cast<size_t>(b->Spad) * 4,
+                           b->stream));
   return RB_OK;
 }
 rb_status fan_before(rb_p2p* b) {
   auto& f = b->fan;
   if (!f.adaptive) return RB_OK;
   if (f.pending && f.since_end >= kFanDecideTicks) {
-    P2P_TRY(b, hipEventSynchronize(f.ev));
+    RB_TRY(b, hipEventSynchronize(f.ev));
     f.pending = false;
     const uint64_t sel = f.host[2] - f.host[0], ld = f.host[3] - f.host[1];
     f.windows += 1;
@@ -713,24 +633,13 @@ rb_status fan_after(rb_p2p* b, int32_t n) {
   if (f.active && f.open && !f.pending && f.ticks >= kFanProbeTicks) {
     rb_status r = fan_snapshot(b, 2);
     if (r != RB_OK) return r;
-    P2P_TRY(b, hipEventRecord(f.ev, b->stream));
+    RB_TRY(b, hipEventRecord(f.ev, b->stream));
     f.pending = true;
     f.since_end = 0;
     f.ticks = 0;
   }
   return RB_OK;
 }
-// hipSetDevice for the batch's calls, the caller's current device restored on every return
-struct DeviceScope {
-  int prev = -1;
-  explicit DeviceScope(int dev) {
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    if (prev != dev) (void)hipSetDevice(dev);
-  }
-  ~DeviceScope() {
-    if (prev >= 0) (void)hipSetDevice(prev);
-  }
-};
 }  // namespace
 
 namespace {
@@ -739,13 +648,12 @@ constexpr const char* kTsOff = "time sync is off (rb_p2p_time_sync_enable)";
 // is idle: the launches before this call may still read the old one.
 rb_status ts_log_reserve(rb_p2p* b, int32_t n) {
   if (n <= b->ts_log_ticks) return RB_OK;
-  P2P_TRY(b, hipStreamSynchronize(b->stream));
-  if (b->ts_log) P2P_TRY(b, hipFree(b->ts_log));
-  b->ts_log = nullptr;
+  RB_TRY(b, hipStreamSynchronize(b->stream));
   b->ts_log_ticks = 0;
+  RB_TRY(b, b->res.release(b->ts_log));
   const size_t bytes = static_cast<size_t>(n) * kTlRows * b->Spad * 4;
-  P2P_TRY(b, hipMalloc(&b->ts_log, bytes));
-  P2P_TRY(b, hipMemsetAsync(b->ts_log, 0xff, bytes, b->stream));  // kTlUnwritten
+  RB_TRY(b, b->res.alloc(b->ts_log, bytes));
+  RB_TRY(b, hipMemsetAsync(b->ts_log, 0xff, bytes, b->stream));  // kTlUnwritten
   b->ts_log_ticks = n;
   return RB_OK;
 }
@@ -756,14 +664,37 @@ rb_status ts_launch(rb_p2p* b, const P2PParams& p, int32_t n, const int32_t* sta
          : b->P == 3 ? p2p_time_sync_kernel<3> : p2p_time_sync_kernel<4>;
   hipLaunchKernelGGL(k, grid, block, 0, b->stream, b->ts, b->ts_log, static_cast<int64_t>(kTlRows) * b->Spad, p.upto, p.upto_stride, status ? status : b->status, n,
                      b->S, b->Spad, p.remote_frames, b->cfg.local_mask, b->cfg.input_delay, b->peer.on);
-  P2P_TRY(b, hipGetLastError());
+  RB_TRY(b, hipGetLastError());
+  return RB_OK;
+}
+
+// What every rb_p2p_run_ticks* call starts with, inside its DeviceScope: the batch's parameters with
+// the caller's tensors, the tick log for `log_ticks` ticks of the call when time sync is on, and the
+// profiling event pair (null when the batch is not profiling; consumed only by prof_ev.commit()).
+rb_status tick_params(rb_p2p* b, int32_t T, const void* local_inputs, int64_t local_stride, const int32_t* remote_upto,
+                      const void* remote_inputs, int32_t remote_frames, int32_t log_ticks, P2PParams& p, LaunchEv& ev) {
+  p = base_params(b);
+  p.local_in = static_cast<const uint8_t*>(local_inputs);
+  p.local_stride = local_stride;
+  p.upto = remote_upto;
+  p.upto_stride = static_cast<int64_t>(b->P) * b->S;
+  p.remote_in = static_cast<const uint8_t*>(remote_inputs);
+  p.remote_frames = remote_frames;
+  p.T = T;
+  if (b->ts_on) {
+    rb_status r = ts_log_reserve(b, log_ticks);
+    if (r != RB_OK) return r;
+    p.tick_log = b->ts_log;
+  }
+  b->ticked = true;
+  if (b->prof) RB_TRY(b, b->prof_ev.next(ev));
   return RB_OK;
 }
 }  // namespace
 
 rb_status rb_p2p_fanout_state(rb_p2p* b, int32_t* active, double* select_fraction, int32_t* windows,
                               int32_t* turned_off) {
-  if (!b->fanout) return pfail(b, RB_INVALID_REQUEST, "the batch has no fan-out");
+  if (!b->fanout) return fail(b, RB_INVALID_REQUEST, "the batch has no fan-out");
   if (active) *active = (!b->fan.adaptive || b->fan.active) ? 1 : 0;
   if (select_fraction) *select_fraction = b->fan.last_frac;
   if (windows) *windows = b->fan.windows;
@@ -775,66 +706,26 @@ rb_status rb_p2p_run_ticks(rb_p2p* b, int32_t n_ticks, const void* local_inputs,
                            const int32_t* remote_upto, const void* remote_inputs, int32_t remote_frames) {
   if (n_ticks <= 0) return RB_OK;
   if (!local_inputs || !remote_upto || !remote_inputs || remote_frames <= 0)
-    return pfail(b, RB_INVALID_REQUEST, "rb_p2p_run_ticks: missing input tensor");
-  P2PParams p = base_params(b);
-  p.local_in = static_cast<const uint8_t*>(local_inputs);
-  p.local_stride = local_stride;
-  p.upto = remote_upto;
-  p.upto_stride = static_cast<int64_t>(b->P) * b->S;
-  p.remote_in = static_cast<const uint8_t*>(remote_inputs);
-  p.remote_frames = remote_frames;
-  p.T = n_ticks;
+    return fail(b, RB_INVALID_REQUEST, "rb_p2p_run_ticks: missing input tensor");
   DeviceScope dev_scope(b->device);
-  if (b->ts_on) {
-    rb_status r = ts_log_reserve(b, n_ticks);
-    if (r != RB_OK) return r;
-    p.tick_log = b->ts_log;
-  }
-  b->ticked = true;
-  if (b->fanout) {
-    rb_status r = fan_before(b);
-    if (r != RB_OK) return r;
-  }
+  P2PParams p;
+  LaunchEv ev;
+  rb_status r = tick_params(b, n_ticks, local_inputs, local_stride, remote_upto, remote_inputs, remote_frames, n_ticks, p, ev);
+  if (r == RB_OK && b->fanout) r = fan_before(b);
+  if (r != RB_OK) return r;
   const bool spec = b->fanout && (!b->fan.adaptive || b->fan.active);
   p.spec_on = spec ? 1 : 0;
-  FanParams fp{};
-  fp.status = b->status;
-  fp.snap = b->snap;
-  fp.tag = b->tag;
-  fp.ring = b->ring;
-  fp.qs = b->qs;
-  fp.spec_state = b->spec_state;
-  fp.spec_cells = b->spec_cells;
-  fp.spec_cs = b->spec_cs;
-  fp.spec_meta = b->spec_meta;
-  fp.stats = b->stats;
-  fp.counters = b->counters;
-  fp.S = b->S;
-  fp.Spad = b->Spad;
-  fp.W = b->W;
-  fp.local_mask = b->cfg.local_mask;
-  fp.fan_generic = b->fan_generic ? 1 : 0;
-  fp.fan_k = b->cfg.fanout_candidates;
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  if (b->prof) {
-    if (b->prof_used == b->prof_ev.size()) {
-      P2P_TRY(b, hipEventCreate(&e0));
-      P2P_TRY(b, hipEventCreate(&e1));
-      b->prof_ev.emplace_back(e0, e1);
-    }
-    e0 = b->prof_ev[b->prof_used].first;
-    e1 = b->prof_ev[b->prof_used].second;
-  }
   const bool one_launch = !spec || (b->ops->inlane_fanout && !b->fan_generic);
   hipError_t e = hipSuccess;
   if (one_launch) {
     // all ticks in one launch (with the in-kernel fan-out); timed by the kernel's own start / end
     p.launch_clock = b->clock.next();
-    e = b->ops->launch_p2p(p, b->block, b->stream, LaunchEv{e0, e1});
+    e = b->ops->launch_p2p(p, b->block, b->stream, ev);
   } else {
-    if (e0) P2P_TRY(b, hipEventRecord(e0, b->stream));
+    if (ev.start) RB_TRY(b, hipEventRecord(ev.start, b->stream));
     // fanout_kernel between ticks needs every lane of a session's branches: one
     // P2P launch and one fan-out launch per tick
+    FanParams fp = fan_params(b);
     P2PParams pt = p;
     pt.T = 1;
     for (int32_t t = 0; t < n_ticks && e == hipSuccess; ++t) {
@@ -847,11 +738,11 @@ rb_status rb_p2p_run_ticks(rb_p2p* b, int32_t n_ticks, const void* local_inputs,
       if (e == hipSuccess) e = b->ops->launch_fanout(fp, b->block, b->stream);
     }
   }
-  if (e != hipSuccess) return pfail(b, RB_DEVICE_ERROR, std::string("p2p launch: ") + hipGetErrorString(e));
-  if (e1 && !one_launch) P2P_TRY(b, hipEventRecord(e1, b->stream));
-  if (e0) ++b->prof_used;  // only a launch that went out has its event pair recorded
+  if (e != hipSuccess) return fail(b, RB_DEVICE_ERROR, std::string("p2p launch: ") + hipGetErrorString(e));
+  if (ev.stop && !one_launch) RB_TRY(b, hipEventRecord(ev.stop, b->stream));
+  if (ev.start) b->prof_ev.commit();  // only a launch that went out has its event pair recorded
   if (b->ts_on) {
-    rb_status r = ts_launch(b, p, n_ticks);
+    r = ts_launch(b, p, n_ticks);
     if (r != RB_OK) return r;
   }
   if (b->fanout) return fan_after(b, n_ticks);
@@ -864,40 +755,21 @@ rb_status rb_p2p_run_ticks_paced(rb_p2p* b, int32_t n_ticks, const void* local_i
   if (!run_mask) return rb_p2p_run_ticks(b, n_ticks, local_inputs, local_stride, remote_upto, remote_inputs, remote_frames);
   if (n_ticks <= 0) return RB_OK;
   if (!local_inputs || !remote_upto || !remote_inputs || remote_frames <= 0)
-    return pfail(b, RB_INVALID_REQUEST, "rb_p2p_run_ticks_paced: missing input tensor");
+    return fail(b, RB_INVALID_REQUEST, "rb_p2p_run_ticks_paced: missing input tensor");
   if (b->fanout)  // the move-to-front rows and branch validity under a parked poll: a later step
-    return pfail(b, RB_INVALID_REQUEST, "rb_p2p_run_ticks_paced: a batch with the fan-out takes rb_p2p_run_ticks");
+    return fail(b, RB_INVALID_REQUEST, "rb_p2p_run_ticks_paced: a batch with the fan-out takes rb_p2p_run_ticks");
   const int IB = b->ops->input_bytes;
-  if (IB != 1 && IB != 4) return pfail(b, RB_INVALID_REQUEST, "rb_p2p_run_ticks_paced: inputs of 1 or 4 bytes");
-  P2PParams p = base_params(b);
-  p.local_in = static_cast<const uint8_t*>(local_inputs);
-  p.local_stride = local_stride;
-  p.upto = remote_upto;
-  p.upto_stride = static_cast<int64_t>(b->P) * b->S;
-  p.remote_in = static_cast<const uint8_t*>(remote_inputs);
-  p.remote_frames = remote_frames;
-  p.T = 1;
+  if (IB != 1 && IB != 4) return fail(b, RB_INVALID_REQUEST, "rb_p2p_run_ticks_paced: inputs of 1 or 4 bytes");
   DeviceScope dev_scope(b->device);
   rb_status r = pace_reserve(b);
   if (r != RB_OK) return r;
-  if (b->ts_on) {
-    r = ts_log_reserve(b, 1);
-    if (r != RB_OK) return r;
-    p.tick_log = b->ts_log;  // one row, consumed by every tick's own time-sync launch
-  }
-  b->ticked = true;
+  P2PParams p;
+  LaunchEv ev;
+  // (one row of the tick log, consumed by every tick's own time-sync launch)
+  r = tick_params(b, 1, local_inputs, local_stride, remote_upto, remote_inputs, remote_frames, 1, p, ev);
+  if (r != RB_OK) return r;
   p.status = b->pace.view;  // parked sessions read as panicked: p2p_kernel returns before any store
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  if (b->prof) {
-    if (b->prof_used == b->prof_ev.size()) {
-      P2P_TRY(b, hipEventCreate(&e0));
-      P2P_TRY(b, hipEventCreate(&e1));
-      b->prof_ev.emplace_back(e0, e1);
-    }
-    e0 = b->prof_ev[b->prof_used].first;
-    e1 = b->prof_ev[b->prof_used].second;
-    P2P_TRY(b, hipEventRecord(e0, b->stream));
-  }
+  if (ev.start) RB_TRY(b, hipEventRecord(ev.start, b->stream));
   const dim3 grid((b->S + 255) / 256), block(256);
   auto poll = IB == 1 ? poll_kernel_of<1>(b->P) : poll_kernel_of<4>(b->P);
   const TimeSyncParams ts = b->ts_on ? b->ts : TimeSyncParams{};
@@ -912,33 +784,33 @@ rb_status rb_p2p_run_ticks_paced(rb_p2p* b, int32_t n_ticks, const void* local_i
     hipLaunchKernelGGL(poll, grid, block, 0, b->stream, b->pace, mask, b->qs, static_cast<uint8_t*>(b->ring), b->status,
                        b->counters, p.upto, p.remote_in, remote_frames, b->cfg.remote_delay, b->cfg.local_mask, ts, b->S,
                        b->Spad);
-    P2P_TRY(b, hipGetLastError());
+    RB_TRY(b, hipGetLastError());
     p.launch_clock = b->clock.next();
     const hipError_t e = b->ops->launch_p2p(p, b->block, b->stream);
-    if (e != hipSuccess) return pfail(b, RB_DEVICE_ERROR, std::string("p2p launch: ") + hipGetErrorString(e));
+    if (e != hipSuccess) return fail(b, RB_DEVICE_ERROR, std::string("p2p launch: ") + hipGetErrorString(e));
     if (b->ts_on) {
       r = ts_launch(b, p, 1, b->pace.view);
       if (r != RB_OK) return r;
     }
     hipLaunchKernelGGL(p2p_unpark_kernel, grid, block, 0, b->stream, b->pace.view, mask, b->status, b->S);
-    P2P_TRY(b, hipGetLastError());
+    RB_TRY(b, hipGetLastError());
   }
-  if (e1) {
-    P2P_TRY(b, hipEventRecord(e1, b->stream));
-    ++b->prof_used;
+  if (ev.stop) {
+    RB_TRY(b, hipEventRecord(ev.stop, b->stream));
+    b->prof_ev.commit();
   }
   return RB_OK;
 }
 
 rb_status rb_p2p_pace(rb_p2p* b, uint8_t* run_mask_dev) {
-  if (!b->ts_on) return pfail(b, RB_INVALID_REQUEST, kTsOff);
-  if (!run_mask_dev) return pfail(b, RB_INVALID_REQUEST, "rb_p2p_pace: missing run mask");
+  if (!b->ts_on) return fail(b, RB_INVALID_REQUEST, kTsOff);
+  if (!run_mask_dev) return fail(b, RB_INVALID_REQUEST, "rb_p2p_pace: missing run mask");
   DeviceScope dev_scope(b->device);
   rb_status r = pace_reserve(b);
   if (r != RB_OK) return r;
   hipLaunchKernelGGL(p2p_pace_kernel, dim3((b->S + 255) / 256), dim3(256), 0, b->stream, b->pace, b->ts.state, b->status,
                      run_mask_dev, b->S, b->Spad);
-  P2P_TRY(b, hipGetLastError());
+  RB_TRY(b, hipGetLastError());
   return RB_OK;
 }
 
@@ -946,7 +818,7 @@ rb_status rb_p2p_read_pacing(rb_p2p* b, uint32_t* parked_ticks) {
   if (!parked_ticks) return RB_OK;
   DeviceScope dev_scope(b->device);
   if (!b->pace.parked) {  // no paced tick yet
-    P2P_TRY(b, hipStreamSynchronize(b->stream));
+    RB_TRY(b, hipStreamSynchronize(b->stream));
     std::memset(parked_ticks, 0, static_cast<size_t>(b->S) * 4);
     return RB_OK;
   }
@@ -962,23 +834,24 @@ rb_status rb_p2p_run_ticks_packets(rb_p2p* b, int32_t n_ticks, const void* local
                                    const int32_t* start_frames, int32_t* decode_status, int32_t* acks) {
   if (n_ticks <= 0) return RB_OK;
   if (!local_inputs || !packets || !lengths || !start_frames)
-    return pfail(b, RB_INVALID_REQUEST, "rb_p2p_run_ticks_packets: missing input tensor");
+    return fail(b, RB_INVALID_REQUEST, "rb_p2p_run_ticks_packets: missing input tensor");
   if (packet_stride < 32 || packet_stride % 16 != 0 || reinterpret_cast<uintptr_t>(packets) % 16 != 0)
-    return pfail(b, RB_INVALID_REQUEST, "rb_p2p_run_ticks_packets: packets need 16-byte alignment and a stride of at least 32");
+    return fail(b, RB_INVALID_REQUEST, "rb_p2p_run_ticks_packets: packets need 16-byte alignment and a stride of at least 32");
   if (b->cfg.sparse_saving || b->fanout || b->ds.interval > 0 || b->peer.on)
-    return pfail(b, RB_INVALID_REQUEST,
-                 "rb_p2p_run_ticks_packets: sparse saving, the fan-out and network reports take rb_p2p_run_ticks");
+    return fail(b, RB_INVALID_REQUEST,
+                "rb_p2p_run_ticks_packets: sparse saving, the fan-out and network reports take rb_p2p_run_ticks");
   if (b->ts_on)  // last_recv_frame is decided inside the kernel there
-    return pfail(b, RB_INVALID_REQUEST, "rb_p2p_run_ticks_packets: time sync takes rb_p2p_run_ticks");
+    return fail(b, RB_INVALID_REQUEST, "rb_p2p_run_ticks_packets: time sync takes rb_p2p_run_ticks");
   // a packet's reference input (frame start - 1) may be as old as the newest received frame -
   // 2 * max_prediction (recv_inputs' retain, protocol.rs:684-686); the 128-entry input queue ring
   // holds the newest 128 frames, so that frame must be younger than last - 127
   if (2 * b->W >= kQueueLen)
-    return pfail(b, RB_INVALID_REQUEST, "rb_p2p_run_ticks_packets: needs 2 * max_prediction < 128 (the input ring)");
-  P2PParams p = base_params(b);
-  p.local_in = static_cast<const uint8_t*>(local_inputs);
-  p.local_stride = local_stride;
-  p.T = n_ticks;
+    return fail(b, RB_INVALID_REQUEST, "rb_p2p_run_ticks_packets: needs 2 * max_prediction < 128 (the input ring)");
+  DeviceScope dev_scope(b->device);
+  P2PParams p;
+  LaunchEv ev;  // the kernel's own start / end (hipExtLaunchKernel)
+  rb_status r = tick_params(b, n_ticks, local_inputs, local_stride, nullptr, nullptr, 0, n_ticks, p, ev);
+  if (r != RB_OK) return r;
   p.packets = packets;
   p.packet_stride = packet_stride;
   p.pk_len = lengths;
@@ -986,27 +859,16 @@ rb_status rb_p2p_run_ticks_packets(rb_p2p* b, int32_t n_ticks, const void* local
   p.pk_status = decode_status;
   p.acks = acks;
   p.launch_clock = b->clock.next();
-  b->ticked = true;
-  DeviceScope dev_scope(b->device);
-  LaunchEv ev;  // the kernel's own start / end (hipExtLaunchKernel)
-  if (b->prof) {
-    if (b->prof_used == b->prof_ev.size()) {
-      hipEvent_t e0 = nullptr, e2 = nullptr;
-      P2P_TRY(b, hipEventCreate(&e0));
-      P2P_TRY(b, hipEventCreate(&e2));
-      b->prof_ev.emplace_back(e0, e2);
-    }
-    ev = LaunchEv{b->prof_ev[b->prof_used].first, b->prof_ev[b->prof_used].second};
-  }
   hipError_t e = b->ops->launch_p2p(p, b->block, b->stream, ev);
-  if (e != hipSuccess) return pfail(b, RB_DEVICE_ERROR, std::string("p2p launch: ") + hipGetErrorString(e));
-  if (ev.start) ++b->prof_used;  // only a launch that went out has its event pair recorded
+  if (e != hipSuccess) return fail(b, RB_DEVICE_ERROR, std::string("p2p launch: ") + hipGetErrorString(e));
+  if (ev.start) b->prof_ev.commit();  // only a launch that went out has its event pair recorded
   return RB_OK;
 }
 
 rb_status rb_p2p_disconnect_player(rb_p2p* b, int32_t handle, const uint8_t* session_mask) {
-  if (handle < 0 || handle >= b->P) return pfail(b, RB_INVALID_REQUEST, "Invalid Player Handle.");
-  if ((b->cfg.local_mask >> handle) & 1u) return pfail(b, RB_INVALID_REQUEST, "Local Player cannot be disconnected.");
+  if (handle < 0 || handle >= b->P) return fail(b, RB_INVALID_REQUEST, "Invalid Player Handle.");
+  if ((b->cfg.local_mask >> handle) & 1u) return fail(b, RB_INVALID_REQUEST, "Local Player cannot be disconnected.");
+  DeviceScope dev_scope(b->device);
   if (b->peer.on || b->mirror_stale) {  // peers' reports disconnect players inside the ticks, an import brings its own: refresh the mirror
     std::vector<int32_t> qs;
     rb_status r = read_rows(b, b->qs, kQsFields, qs);
@@ -1018,41 +880,28 @@ rb_status rb_p2p_disconnect_player(rb_p2p* b, int32_t handle, const uint8_t* ses
   }
   uint8_t* d = b->disconnected.data() + static_cast<size_t>(handle) * b->S;
   for (int s = 0; s < b->S; ++s)
-    if ((!session_mask || session_mask[s]) && d[s]) return pfail(b, RB_INVALID_REQUEST, "Player already disconnected.");
+    if ((!session_mask || session_mask[s]) && d[s]) return fail(b, RB_INVALID_REQUEST, "Player already disconnected.");
   for (int s = 0; s < b->S; ++s)
     if (!session_mask || session_mask[s]) d[s] = 1;
-  P2P_TRY(b, hipSetDevice(b->device));
   if (session_mask) {
-    P2P_TRY(b, hipMemcpyAsync(b->disc_mask, session_mask, b->S, hipMemcpyHostToDevice, b->stream));
-    P2P_TRY(b, hipStreamSynchronize(b->stream));  // the host mask may be reused as soon as we return
+    RB_TRY(b, hipMemcpyAsync(b->disc_mask, session_mask, b->S, hipMemcpyHostToDevice, b->stream));
+    RB_TRY(b, hipStreamSynchronize(b->stream));  // the host mask may be reused as soon as we return
   }
   const int blocks = (b->S + 255) / 256;
   hipLaunchKernelGGL(p2p_disconnect_kernel, dim3(blocks), dim3(256), 0, b->stream, b->qs,
                      session_mask ? b->disc_mask : nullptr, b->S, b->Spad, handle);
-  P2P_TRY(b, hipGetLastError());
+  RB_TRY(b, hipGetLastError());
   return RB_OK;
 }
 
 rb_status rb_p2p_restart_sessions(rb_p2p* b, const uint8_t* session_mask) {
   std::vector<int32_t> idx;
-  if (session_mask) {
-    restart_selected(session_mask, b->S, idx);
-    if (idx.empty()) return RB_OK;
-  }
-  const bool all = !session_mask || idx.size() == static_cast<size_t>(b->S);
-  DeviceScope dev_scope(b->device);
-  PlaneSet ps;
-  all_planes(b, ps);
-  if (ps.tmpl != b->tmpl_host) return pfail(b, RB_DEVICE_ERROR, "rb_p2p_restart_sessions: the templates moved since create");
-  ps.bind(b->tmpl);
-  if (!all) P2P_TRY(b, b->restart_idx.upload(idx, static_cast<size_t>(b->S), b->stream));
-  P2P_TRY(b, restart_launch(ps, all ? nullptr : b->restart_idx.dev, all ? static_cast<uint32_t>(b->S) : static_cast<uint32_t>(idx.size()),
-                            b->stream));
+  const rb_status r = restart_sessions(b, session_mask, idx);
+  if (r != RB_OK) return r;
   // the host mirror of ConnectionStatus::disconnected
-  if (all) std::fill(b->disconnected.begin(), b->disconnected.end(), uint8_t{0});
-  else
-    for (int h = 0; h < b->P; ++h)
-      for (int32_t s : idx) b->disconnected[static_cast<size_t>(h) * b->S + s] = 0;
+  if (!session_mask) std::fill(b->disconnected.begin(), b->disconnected.end(), uint8_t{0});
+  for (int h = 0; h < b->P; ++h)
+    for (int32_t s : idx) b->disconnected[static_cast<size_t>(h) * b->S + s] = 0;
   return RB_OK;
 }
 
@@ -1060,7 +909,8 @@ rb_status rb_p2p_restart_sessions(rb_p2p* b, const uint8_t* session_mask) {
 // ordinary movable Rust value.
 
 // The configuration the kernels compile in or read: a record goes only into a batch that agrees.
-static std::vector<uint32_t> record_config(const rb_p2p* b) {
+std::vector<uint32_t> rb_p2p::record_config() const {
+  const rb_p2p* const b = this;
   const GameOps& o = *b->ops;
   return {1u /* a P2P batch */,
           static_cast<uint32_t>(b->cfg.game),
@@ -1083,47 +933,16 @@ static std::vector<uint32_t> record_config(const rb_p2p* b) {
           b->fanout ? static_cast<uint32_t>(b->cfg.fanout_candidates) : 0u};
 }
 
-// Every per-session plane the batch's configuration can have, the carry-only ones included.
-// layout_only: without making the lazily made groups (their planes have no buffers).
-static RecordLayout record_planes(const rb_p2p* b, PlaneSet& ps, bool layout_only) {
-  ps.carry = true;
-  ps.layout_only = layout_only;
-  all_planes(b, ps);
-  return record_layout(plane_shapes(ps), record_config(b));
-}
-
-static rb_status move_sessions(rb_p2p* b, const int32_t* sessions, int32_t n, void* records, bool scatter) {
-  const char* const who = scatter ? "rb_p2p_import_sessions" : "rb_p2p_export_sessions";
-  if (n < 0 || (n > 0 && (!sessions || !records))) return pfail(b, RB_INVALID_REQUEST, std::string(who) + ": missing session list or records");
-  if (!move_indices_ok(sessions, n, b->S))
-    return pfail(b, RB_INVALID_REQUEST, std::string(who) + ": sessions must be distinct indices in [0, num_sessions)");
-  if (n == 0) return RB_OK;
-  if (reinterpret_cast<uintptr_t>(records) % 16 != 0)
-    return pfail(b, RB_INVALID_REQUEST, std::string(who) + ": records need 16-byte alignment");
-  DeviceScope dev_scope(b->device);
-  // the groups a later call would make, with create's fresh values: record_bytes depends on the
-  // configuration only, and no read-back of a batch that never paces or exports changes
-  rb_status r = export_reserve(b);
-  if (r == RB_OK && !b->fanout) r = pace_reserve(b);
-  if (r != RB_OK) return r;
-  if (scatter && !b->refused) {
-    P2P_TRY(b, hipMalloc(&b->refused, 4));
-    P2P_TRY(b, hipMemsetAsync(b->refused, 0, 4, b->stream));
-  }
-  PlaneSet ps;
-  const RecordLayout lay = record_planes(b, ps, false);
-  P2P_TRY(b, b->move_idx.upload(std::vector<int32_t>(sessions, sessions + n), static_cast<size_t>(b->S), b->stream));
-  P2P_TRY(b, move_launch(ps, lay, b->move_idx.dev, static_cast<uint32_t>(n), records, scatter, b->refused, b->stream));
-  if (scatter) {
-    b->ticked = true;        // the columns hold a running match: rb_p2p_time_sync_enable is closed
-    b->mirror_stale = true;  // ConnectionStatus::disconnected arrived in qs
-  }
-  return RB_OK;
+// the groups a later call would make, with create's fresh values: record_bytes depends on the
+// configuration only, and no read-back of a batch that never paces or exports changes
+rb_status rb_p2p::before_move() {
+  const rb_status r = export_reserve(this);
+  return r == RB_OK && !fanout ? pace_reserve(this) : r;
 }
 
 int64_t rb_p2p_session_record_bytes(const rb_p2p* b) {
-  PlaneSet ps;
-  return static_cast<int64_t>(record_planes(b, ps, true).record_bytes);
+  PlaneSet ps;  // (layout only: nothing of the batch is written)
+  return static_cast<int64_t>(record_planes(const_cast<rb_p2p*>(b), ps, true).record_bytes);
 }
 
 rb_status rb_p2p_export_sessions(rb_p2p* b, const int32_t* sessions, int32_t n, void* records_dev) {
@@ -1131,18 +950,15 @@ rb_status rb_p2p_export_sessions(rb_p2p* b, const int32_t* sessions, int32_t n, 
 }
 
 rb_status rb_p2p_import_sessions(rb_p2p* b, const int32_t* sessions, int32_t n, const void* records_dev) {
-  return move_sessions(b, sessions, n, const_cast<void*>(records_dev), true);
+  const rb_status r = move_sessions(b, sessions, n, const_cast<void*>(records_dev), true);
+  if (r == RB_OK && n > 0) {
+    b->ticked = true;        // the columns hold a running match: rb_p2p_time_sync_enable is closed
+    b->mirror_stale = true;  // ConnectionStatus::disconnected arrived in qs
+  }
+  return r;
 }
 
-rb_status rb_p2p_import_refused(rb_p2p* b, uint32_t* count) {
-  if (!count) return RB_OK;
-  *count = 0;
-  if (!b->refused) return RB_OK;  // no import yet
-  DeviceScope dev_scope(b->device);
-  P2P_TRY(b, hipMemcpyAsync(count, b->refused, 4, hipMemcpyDeviceToHost, b->stream));
-  P2P_TRY(b, hipStreamSynchronize(b->stream));
-  return RB_OK;
-}
+rb_status rb_p2p_import_refused(rb_p2p* b, uint32_t* count) { return import_refused(b, count); }
 
 rb_status rb_p2p_read_status(rb_p2p* b, int32_t* status, int32_t* load_frame, int32_t* n_adv, int32_t* n_save) {
   std::vector<int32_t> st, tr, cur;
@@ -1197,12 +1013,13 @@ rb_status rb_p2p_read_queues(rb_p2p* b, int32_t* out) {
 }
 
 rb_status rb_p2p_read_cells(rb_p2p* b, int32_t* tags, void* images, uint64_t* checksums) {
+  DeviceScope dev_scope(b->device);
   std::vector<int32_t> tg;
   rb_status r = read_rows(b, b->tag, b->W, tg);
   if (r != RB_OK) return r;
   const size_t Sp = b->Spad, L = b->ops->lanes, NW = b->ops->nw, B = b->ops->image_bytes;
   std::vector<uint8_t> csh(b->W * Sp * b->ops->cs_bytes);
-  P2P_TRY(b, hipMemcpy(csh.data(), b->cs, csh.size(), hipMemcpyDeviceToHost));
+  RB_TRY(b, hipMemcpy(csh.data(), b->cs, csh.size(), hipMemcpyDeviceToHost));
   std::vector<uint32_t> planes;
   for (int w = 0; w < b->W; ++w) {
     if (images) {
@@ -1237,8 +1054,9 @@ rb_status rb_p2p_read_live(rb_p2p* b, void* images) {
 
 rb_status rb_p2p_counters(rb_p2p* b, uint32_t* out3) {
   uint32_t c[4];
-  P2P_TRY(b, hipStreamSynchronize(b->stream));
-  P2P_TRY(b, hipMemcpy(c, b->counters, 16, hipMemcpyDeviceToHost));
+  DeviceScope dev_scope(b->device);
+  RB_TRY(b, hipStreamSynchronize(b->stream));
+  RB_TRY(b, hipMemcpy(c, b->counters, 16, hipMemcpyDeviceToHost));
   for (int i = 0; i < 3; ++i) out3[i] = c[i];
   return RB_OK;
 }
@@ -1256,52 +1074,52 @@ rb_status rb_p2p_totals(rb_p2p* b, uint64_t* out5) {
 }
 
 rb_status rb_p2p_take_checksum_reports(rb_p2p* b, void* dev_out) {
-  if (b->ds.interval <= 0) return pfail(b, RB_INVALID_REQUEST, "desync detection is off (desync_interval = 0)");
-  P2P_TRY(b, hipSetDevice(b->device));
+  if (b->ds.interval <= 0) return fail(b, RB_INVALID_REQUEST, "desync detection is off (desync_interval = 0)");
+  DeviceScope dev_scope(b->device);
   hipLaunchKernelGGL(p2p_take_reports_kernel, dim3((b->S + 255) / 256), dim3(256), 0, b->stream, b->ds,
                      static_cast<rb_checksum_report*>(dev_out), b->S, b->Spad);
-  P2P_TRY(b, hipGetLastError());
+  RB_TRY(b, hipGetLastError());
   return RB_OK;
 }
 
 rb_status rb_p2p_receive_checksum_reports(rb_p2p* b, int32_t handle, const void* dev_in, int32_t count) {
-  if (b->ds.interval <= 0) return pfail(b, RB_INVALID_REQUEST, "desync detection is off (desync_interval = 0)");
+  if (b->ds.interval <= 0) return fail(b, RB_INVALID_REQUEST, "desync detection is off (desync_interval = 0)");
   if (handle < 0 || handle >= b->P || ((b->cfg.local_mask >> handle) & 1u))
-    return pfail(b, RB_INVALID_REQUEST, "checksum reports come from a remote handle's endpoint");
+    return fail(b, RB_INVALID_REQUEST, "checksum reports come from a remote handle's endpoint");
   if (count <= 0) return RB_OK;
-  P2P_TRY(b, hipSetDevice(b->device));
+  DeviceScope dev_scope(b->device);
   hipLaunchKernelGGL(p2p_receive_reports_kernel, dim3((b->S + 255) / 256), dim3(256), 0, b->stream, b->ds,
                      static_cast<const rb_checksum_report*>(dev_in), count, b->S, b->Spad, handle);
-  P2P_TRY(b, hipGetLastError());
+  RB_TRY(b, hipGetLastError());
   return RB_OK;
 }
 
 rb_status rb_p2p_receive_peer_connect_status(rb_p2p* b, int32_t endpoint, const int32_t* last_frames,
                                              const uint8_t* disconnected) {
-  if (!b->peer.on) return pfail(b, RB_INVALID_REQUEST, "peer connect status needs RB_P2P_FLAG_PEER_STATUS");
+  if (!b->peer.on) return fail(b, RB_INVALID_REQUEST, "peer connect status needs RB_P2P_FLAG_PEER_STATUS");
   if (endpoint < 0 || endpoint >= b->P || ((b->cfg.local_mask >> endpoint) & 1u))
-    return pfail(b, RB_INVALID_REQUEST, "connect-status reports come from a remote handle's endpoint");
-  if (!last_frames || !disconnected) return pfail(b, RB_INVALID_REQUEST, "missing connect-status tensor");
-  P2P_TRY(b, hipSetDevice(b->device));
+    return fail(b, RB_INVALID_REQUEST, "connect-status reports come from a remote handle's endpoint");
+  if (!last_frames || !disconnected) return fail(b, RB_INVALID_REQUEST, "missing connect-status tensor");
+  DeviceScope dev_scope(b->device);
   hipLaunchKernelGGL(p2p_peer_status_kernel, dim3((b->S + 255) / 256), dim3(256), 0, b->stream, b->peer, last_frames,
                      disconnected, b->S, b->Spad, b->P, endpoint);
-  P2P_TRY(b, hipGetLastError());
+  RB_TRY(b, hipGetLastError());
   return RB_OK;
 }
 
 rb_status rb_p2p_export_confirmed_inputs(rb_p2p* b, void* inputs_by_frame, int32_t frames, int32_t* upto,
                                          int32_t* last_frames, uint8_t* disconnected) {
   if (!inputs_by_frame || !upto || !last_frames || !disconnected || frames <= 0)
-    return pfail(b, RB_INVALID_REQUEST, "rb_p2p_export_confirmed_inputs: missing output tensor");
+    return fail(b, RB_INVALID_REQUEST, "rb_p2p_export_confirmed_inputs: missing output tensor");
   DeviceScope dev_scope(b->device);
   if (rb_status r = export_reserve(b); r != RB_OK) return r;
   const dim3 grid((b->S + 255) / 256), block(256);
   auto k = b->ops->input_bytes == 4 ? p2p_export_kernel<4> : p2p_export_kernel<1>;
   if (b->ops->input_bytes != 4 && b->ops->input_bytes != 1)
-    return pfail(b, RB_INVALID_REQUEST, "rb_p2p_export_confirmed_inputs: 1- and 4-byte inputs");
+    return fail(b, RB_INVALID_REQUEST, "rb_p2p_export_confirmed_inputs: 1- and 4-byte inputs");
   hipLaunchKernelGGL(k, grid, block, 0, b->stream, b->qs, static_cast<const uint8_t*>(b->ring), b->status, b->exp_state,
                      b->S, b->Spad, b->P, static_cast<uint8_t*>(inputs_by_frame), frames, upto, last_frames, disconnected);
-  P2P_TRY(b, hipGetLastError());
+  RB_TRY(b, hipGetLastError());
   return RB_OK;
 }
 
@@ -1325,52 +1143,43 @@ rb_status rb_p2p_read_export_status(rb_p2p* b, int32_t* status, int32_t* next_fr
 
 // ---- time sync (time_sync.hpp)
 rb_status rb_p2p_time_sync_enable(rb_p2p* b, int32_t fps) {
-  if (fps <= 0) return pfail(b, RB_INVALID_REQUEST, "FPS should be higher than 0.");  // builder.rs:190-194
-  if (b->ts_on) return pfail(b, RB_INVALID_REQUEST, "rb_p2p_time_sync_enable: time sync is already on");
-  if (b->ticked) return pfail(b, RB_INVALID_REQUEST, "rb_p2p_time_sync_enable: comes before the batch's first tick");
+  if (fps <= 0) return fail(b, RB_INVALID_REQUEST, "FPS should be higher than 0.");  // builder.rs:190-194
+  if (b->ts_on) return fail(b, RB_INVALID_REQUEST, "rb_p2p_time_sync_enable: time sync is already on");
+  if (b->ticked) return fail(b, RB_INVALID_REQUEST, "rb_p2p_time_sync_enable: comes before the batch's first tick");
   if (b->cfg.game >= RB_GAME_PLUGIN_BASE && !plugin_writes_tick_log(b->cfg.game))
-    return pfail(b, RB_INVALID_REQUEST, "rb_p2p_time_sync_enable: rebuild the game plugin against the current headers");
+    return fail(b, RB_INVALID_REQUEST, "rb_p2p_time_sync_enable: rebuild the game plugin against the current headers");
   DeviceScope dev_scope(b->device);
-  const size_t st = static_cast<size_t>(TS_ROWS) * b->Spad * 4, wn = 2ull * kTsWindow * 4 * b->Spad * 4;
-  int32_t *state = nullptr, *win = nullptr;
-  P2P_TRY(b, hipMalloc(&state, st));
-  if (hipError_t e = hipMalloc(&win, wn); e != hipSuccess) {
-    (void)hipFree(state);
-    return pfail(b, RB_DEVICE_ERROR, std::string("hipMalloc: ") + hipGetErrorString(e));
-  }
-  b->ts.state = state;
-  b->ts.win = win;
   b->ts.fps = fps;
-  P2P_TRY(b, fill_group(b, time_sync_planes));
+  if (const rb_status r = make_group(b, time_sync_planes); r != RB_OK) return r;
   b->ts_on = true;
   return RB_OK;
 }
 
 rb_status rb_p2p_receive_quality(rb_p2p* b, int32_t handle, const int32_t* rtt_ms, const int32_t* frame_advantage) {
-  if (!b->ts_on) return pfail(b, RB_INVALID_REQUEST, kTsOff);
+  if (!b->ts_on) return fail(b, RB_INVALID_REQUEST, kTsOff);
   if (handle < 0 || handle >= b->P || ((b->cfg.local_mask >> handle) & 1u))
-    return pfail(b, RB_INVALID_REQUEST, "quality reports come from a remote handle's endpoint");
+    return fail(b, RB_INVALID_REQUEST, "quality reports come from a remote handle's endpoint");
   if (!rtt_ms && !frame_advantage) return RB_OK;
   DeviceScope dev_scope(b->device);
   hipLaunchKernelGGL(p2p_receive_quality_kernel, dim3((b->S + 255) / 256), dim3(256), 0, b->stream, b->ts, rtt_ms,
                      frame_advantage, b->S, b->Spad, handle);
-  P2P_TRY(b, hipGetLastError());
+  RB_TRY(b, hipGetLastError());
   return RB_OK;
 }
 
 rb_status rb_p2p_export_time_sync(rb_p2p* b, int32_t* frames_ahead_dev, int32_t* local_adv_dev) {
-  if (!b->ts_on) return pfail(b, RB_INVALID_REQUEST, kTsOff);
+  if (!b->ts_on) return fail(b, RB_INVALID_REQUEST, kTsOff);
   if (!frames_ahead_dev && !local_adv_dev) return RB_OK;
   DeviceScope dev_scope(b->device);
   hipLaunchKernelGGL(p2p_export_time_sync_kernel, dim3((b->S + 255) / 256), dim3(256), 0, b->stream, b->ts,
                      frames_ahead_dev, local_adv_dev, b->S, b->Spad, b->P);
-  P2P_TRY(b, hipGetLastError());
+  RB_TRY(b, hipGetLastError());
   return RB_OK;
 }
 
 rb_status rb_p2p_read_time_sync(rb_p2p* b, int32_t* frames_ahead, int32_t* local_adv, int32_t* remote_adv,
                                 int32_t* rtt_ms) {
-  if (!b->ts_on) return pfail(b, RB_INVALID_REQUEST, kTsOff);
+  if (!b->ts_on) return fail(b, RB_INVALID_REQUEST, kTsOff);
   DeviceScope dev_scope(b->device);
   std::vector<int32_t> st;
   rb_status r = read_rows(b, b->ts.state, TS_ROWS, st);
@@ -1389,7 +1198,7 @@ rb_status rb_p2p_read_time_sync(rb_p2p* b, int32_t* frames_ahead, int32_t* local
 }
 
 rb_status rb_p2p_read_wait_recommendations(rb_p2p* b, uint32_t* counts, int32_t* frames, int32_t* skip_frames) {
-  if (!b->ts_on) return pfail(b, RB_INVALID_REQUEST, kTsOff);
+  if (!b->ts_on) return fail(b, RB_INVALID_REQUEST, kTsOff);
   static_assert(kTsEvents == RB_P2P_WAIT_EVENTS_KEPT, "the event ring of time_sync.hpp");
   DeviceScope dev_scope(b->device);
   std::vector<int32_t> st;
@@ -1410,7 +1219,7 @@ rb_status rb_p2p_read_wait_recommendations(rb_p2p* b, uint32_t* counts, int32_t*
 }
 
 rb_status rb_p2p_debug_read_time_sync_windows(rb_p2p* b, int32_t* out) {
-  if (!b->ts_on) return pfail(b, RB_INVALID_REQUEST, kTsOff);
+  if (!b->ts_on) return fail(b, RB_INVALID_REQUEST, kTsOff);
   DeviceScope dev_scope(b->device);
   std::vector<int32_t> w;
   rb_status r = read_rows(b, b->ts.win, 2 * static_cast<size_t>(kTsWindow) * 4, w);
@@ -1433,22 +1242,21 @@ rb_status rb_debug_time_sync_average(int32_t device, const int32_t* local_sums, 
   }
   DeviceScope dev_scope(device);
   const size_t bytes = static_cast<size_t>(n) * 4;
+  DeviceOwner tmp;  // freed on every return
   int32_t* d = nullptr;
-  if (hipMalloc(&d, 3 * bytes) != hipSuccess) return RB_DEVICE_ERROR;
-  bool ok = hipMemcpy(d, local_sums, bytes, hipMemcpyHostToDevice) == hipSuccess &&
-            hipMemcpy(d + n, remote_sums, bytes, hipMemcpyHostToDevice) == hipSuccess;
-  if (ok) {
-    hipLaunchKernelGGL(time_sync_average_kernel, dim3(static_cast<unsigned>((n + 255) / 256)), dim3(256), 0, nullptr, d,
-                       d + n, d + 2 * n, n);
-    ok = hipGetLastError() == hipSuccess && hipMemcpy(out, d + 2 * n, bytes, hipMemcpyDeviceToHost) == hipSuccess;
-  }
-  (void)hipFree(d);
+  if (tmp.alloc(d, 3 * bytes) != hipSuccess) return RB_DEVICE_ERROR;
+  if (hipMemcpy(d, local_sums, bytes, hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemcpy(d + n, remote_sums, bytes, hipMemcpyHostToDevice) != hipSuccess)
+    return RB_DEVICE_ERROR;
+  hipLaunchKernelGGL(time_sync_average_kernel, dim3(static_cast<unsigned>((n + 255) / 256)), dim3(256), 0, nullptr, d,
+                     d + n, d + 2 * n, n);
+  const bool ok = hipGetLastError() == hipSuccess && hipMemcpy(out, d + 2 * n, bytes, hipMemcpyDeviceToHost) == hipSuccess;
   return ok ? RB_OK : RB_DEVICE_ERROR;
 }
 
 rb_status rb_p2p_read_desync_events(rb_p2p* b, uint32_t* counts, int32_t* frames, int32_t* handles,
                                     uint64_t* local_checksums, uint64_t* remote_checksums) {
-  if (b->ds.interval <= 0) return pfail(b, RB_INVALID_REQUEST, "desync detection is off (desync_interval = 0)");
+  if (b->ds.interval <= 0) return fail(b, RB_INVALID_REQUEST, "desync detection is off (desync_interval = 0)");
   const size_t Sp = b->Spad, E = kEvents;
   std::vector<uint32_t> n;
   std::vector<int32_t> fr, hd;
@@ -1476,75 +1284,51 @@ rb_status rb_p2p_read_desync_events(rb_p2p* b, uint32_t* counts, int32_t* frames
 
 rb_status rb_p2p_debug_corrupt(rb_p2p* b, int32_t session, int32_t word, uint32_t xor_mask) {
   if (session < 0 || session >= b->S || word < 0 || word >= b->ops->canon_words)
-    return pfail(b, RB_INVALID_REQUEST, "rb_p2p_debug_corrupt: session or word out of range");
+    return fail(b, RB_INVALID_REQUEST, "rb_p2p_debug_corrupt: session or word out of range");
   int lane = 0, w = 0;
   b->ops->word_loc(word, &lane, &w);
   const int L = b->ops->lanes, NW = b->ops->nw;
   const size_t idx = word_index(NW, b->Spad * L, session * L + lane, w);
-  P2P_TRY(b, hipSetDevice(b->device));
-  P2P_TRY(b, hipStreamSynchronize(b->stream));
+  DeviceScope dev_scope(b->device);
+  RB_TRY(b, hipStreamSynchronize(b->stream));
   const size_t plane = static_cast<size_t>(NW) * b->Spad * L;
   std::vector<uint32_t*> where{b->live + idx};
   for (int k = 0; k < b->W; ++k) where.push_back(b->snap + k * plane + idx);
   for (uint32_t* q : where) {
     uint32_t v = 0;
-    P2P_TRY(b, hipMemcpy(&v, q, 4, hipMemcpyDeviceToHost));
+    RB_TRY(b, hipMemcpy(&v, q, 4, hipMemcpyDeviceToHost));
     v ^= xor_mask;
-    P2P_TRY(b, hipMemcpy(q, &v, 4, hipMemcpyHostToDevice));
+    RB_TRY(b, hipMemcpy(q, &v, 4, hipMemcpyHostToDevice));
   }
   return RB_OK;
 }
 
 rb_status rb_p2p_launch_clock_arm(rb_p2p* b, int32_t launches) {
-  if (launches <= 0) return pfail(b, RB_INVALID_REQUEST, "rb_p2p_launch_clock_arm: no launches");
+  if (launches <= 0) return fail(b, RB_INVALID_REQUEST, "rb_p2p_launch_clock_arm: no launches");
   DeviceScope dev_scope(b->device);
-  // one slot holds the widest launch of the batch: fanout_kernel's 16 branches per session
+  // one slot holds every wave of the widest launch of the batch: fanout_kernel's 16 branches per session
   const size_t lanes = static_cast<size_t>(b->Spad) * b->ops->lanes * (b->fanout ? kSpecBranches : 1);
-  P2P_TRY(b, b->clock.arm((lanes + 63) / 64, static_cast<size_t>(launches), b->stream));
+  RB_TRY(b, b->clock.arm(b->res, launch_waves(lanes, b->block), static_cast<size_t>(launches), b->stream));
   return RB_OK;
 }
 
 rb_status rb_p2p_launch_clock_read(rb_p2p* b, uint64_t* start_end, int32_t cap, int32_t* launches) {
-  if (!b->clock.armed) return pfail(b, RB_INVALID_REQUEST, "rb_p2p_launch_clock_read: not armed");
+  if (!b->clock.armed) return fail(b, RB_INVALID_REQUEST, "rb_p2p_launch_clock_read: not armed");
   DeviceScope dev_scope(b->device);
-  P2P_TRY(b, b->clock.read(start_end, cap, launches, b->stream));
+  RB_TRY(b, b->clock.read(start_end, cap, launches, b->stream));
   return RB_OK;
 }
 
 rb_status rb_p2p_profile_enable(rb_p2p* b, int32_t on) {
   b->prof = on != 0;
-  // the event pool is created here, outside any timed region
-  if (b->prof) {
-    P2P_TRY(b, hipSetDevice(b->device));
-    const size_t fresh = b->prof_ev.size();
-    while (b->prof_ev.size() < 256) {
-      hipEvent_t e0 = nullptr, e1 = nullptr;
-      P2P_TRY(b, hipEventCreate(&e0));
-      P2P_TRY(b, hipEventCreate(&e1));
-      b->prof_ev.emplace_back(e0, e1);
-    }
-    for (size_t i = fresh; i < b->prof_ev.size(); ++i) {  // first records (signal set-up) outside timed regions
-      P2P_TRY(b, hipEventRecord(b->prof_ev[i].first, b->stream));
-      P2P_TRY(b, hipEventRecord(b->prof_ev[i].second, b->stream));
-    }
-    P2P_TRY(b, hipStreamSynchronize(b->stream));
-  }
+  if (!b->prof) return RB_OK;
+  DeviceScope dev_scope(b->device);
+  RB_TRY(b, b->prof_ev.enable(b->stream));
   return RB_OK;
 }
 
 rb_status rb_p2p_profile_take(rb_p2p* b, double* total_ms, int32_t* launches) {
-  double t = 0;
-  if (b->prof_used > 0) {
-    P2P_TRY(b, hipEventSynchronize(b->prof_ev[b->prof_used - 1].second));
-    for (size_t i = 0; i < b->prof_used; ++i) {
-      float ms = 0;
-      P2P_TRY(b, hipEventElapsedTime(&ms, b->prof_ev[i].first, b->prof_ev[i].second));
-      t += ms;
-    }
-  }
-  if (total_ms) *total_ms = t;
-  if (launches) *launches = static_cast<int32_t>(b->prof_used);
-  b->prof_used = 0;
+  RB_TRY(b, b->prof_ev.take(total_ms, nullptr, launches));
   return RB_OK;
 }
 

@@ -6,12 +6,17 @@
 // Spad * lanes) elements, a session's value at its own column of every row.  A
 // PlaneSet lists a batch's planes with what a fresh column holds; the engines
 // describe each buffer group in one function (p2p_engine.hip *_planes,
-// spectator_engine.hip spectator_planes) and run restart_kernel over the set
-//   - for every column when the group's buffers are made (rb_p2p_create,
+// spectator_engine.hip spectator_planes).  That function is the only
+// description of a per-session buffer: run with `make` set it allocates every
+// buffer that does not exist yet, through the batch's owner (host_batch.hpp),
+// with the extent the plane's own shape gives, so the size restart_kernel and
+// the move kernels write by is the size that was allocated.  restart_kernel
+// then runs over the set
+//   - for every column when the group's buffers are made (create,
 //     rb_p2p_time_sync_enable, the first paced tick, the first export), and
 //   - for the selected sessions' columns in a restart,
 // so a restarted session holds what a created one does by construction: there
-// is no second list of initial values.
+// is no second list of initial values or of sizes.
 //
 // restart_kernel is game independent.  It is defined in the one translation
 // unit that sets RB_RESTART_DEFINE (p2p_engine.hip); the others link to
@@ -23,6 +28,8 @@
 #include <vector>
 
 #include <hip/hip_runtime.h>
+
+#include "host_batch.hpp"
 
 namespace rb {
 
@@ -66,20 +73,6 @@ inline void restart_selected(const uint8_t* mask, int n, std::vector<int32_t>& i
     if (mask[s]) idx.push_back(s);
 }
 
-// The state planes' layout (kernels.hpp word_index): a lane column's NW words lie in groups of
-// four (16-byte elements), then a pair (8 bytes), then a single word.  The same function gives the
-// layout of a one-session batch, which is the form the live state's template is kept in.
-inline size_t restart_word_index(int NW, size_t cols, size_t c, int k) {
-  const int Q4 = NW / 4, R = NW % 4;
-  if (k < Q4 * 4) return static_cast<size_t>(k / 4) * 4 * cols + c * 4 + (k % 4);
-  size_t b = static_cast<size_t>(Q4) * 4 * cols;
-  if (R >= 2) {
-    if (k < Q4 * 4 + 2) return b + c * 2 + (k - Q4 * 4);
-    b += 2 * cols;
-  }
-  return b + c;
-}
-
 // A batch's planes under construction: the descriptors, and the template words they refer to by
 // offset until bind() points them into the device copy of `tmpl`.
 //
@@ -95,6 +88,8 @@ struct PlaneSet {
   size_t Spad = 0;
   bool carry = false;        // list the carry-only planes too
   bool layout_only = false;  // list the groups a later call makes as well, with no buffers: for a record's layout
+  DeviceOwner* make = nullptr;  // allocate the listed buffers that do not exist yet
+  hipError_t err = hipSuccess;  // the first allocation that failed
   std::vector<RestartPlane> planes;
   std::vector<uint8_t> kind;  // per plane
   std::vector<uint32_t> tmpl;
@@ -102,8 +97,15 @@ struct PlaneSet {
 
   static constexpr size_t npos = ~size_t{0};
 
-  // [groups][rows_in][Spad * cps] elements, every fresh element the byte `fill_byte` repeated
-  void fill(void* base, int esize, size_t rows, int cps, uint8_t fill_byte) {
+  // The extent of one buffer: [rows][Spad * cps] elements.  Every function below that takes a
+  // buffer by reference declares it so, from the shape it lists; a buffer that several planes share,
+  // or that none lists, is declared here once, by its group function.
+  template <class T>
+  void buffer(T*& p, int esize, size_t rows, int cps) {
+    if (make && !p && err == hipSuccess) err = make->alloc(p, rows * Spad * cps * esize);
+  }
+  // rows [rows][Spad * cps] at `base`, inside a declared buffer
+  void plane(void* base, int esize, size_t rows, int cps, uint8_t fill_byte) {
     RestartPlane q{};
     q.base = static_cast<char*>(base);
     q.stride = static_cast<unsigned long long>(Spad) * cps * esize;
@@ -118,24 +120,34 @@ struct PlaneSet {
     kind.push_back(kPlaneFresh);
     tmpl_off.push_back(npos);
   }
+  // [rows][Spad * cps] elements, every fresh element the byte `fill_byte` repeated
+  template <class T>
+  void fill(T*& base, int esize, size_t rows, int cps, uint8_t fill_byte) {
+    buffer(base, esize, rows, cps);
+    plane(base, esize, rows, cps, fill_byte);
+  }
   // [rows][Spad * cps] elements with no fresh value: carried by a move, skipped otherwise
-  void carried(void* base, int esize, size_t rows, int cps) {
+  template <class T>
+  void carried(T*& base, int esize, size_t rows, int cps) {
+    buffer(base, esize, rows, cps);
     if (!carry) return;
-    fill(base, esize, rows, cps, 0);
+    plane(base, esize, rows, cps, 0);
     kind.back() = kPlaneCarryOnly;
   }
   // the last plane (a fill) is not carried by a move: the record holds its fresh value
   void fresh_on_move() { kind.back() = kPlaneFreshOnMove; }
   // [groups][rows][Spad] words, row r of every group `values[r]`
-  void row_values(int32_t* base, size_t groups, const std::vector<int32_t>& values) {
-    fill(base, 4, values.size(), 1, 0);
+  void row_values(int32_t*& base, size_t groups, const std::vector<int32_t>& values) {
+    buffer(base, 4, groups * values.size(), 1);
+    plane(base, 4, values.size(), 1, 0);
     planes.back().groups = static_cast<uint32_t>(groups);
     tmpl_off.back() = tmpl.size() * 4;
     for (int32_t v : values) tmpl.push_back(static_cast<uint32_t>(v));
   }
-  // State planes (restart_word_index) of `cells` cells of NW words for Spad * L lane columns:
+  // State planes (word_index) of `cells` cells of NW words for Spad * L lane columns:
   // zero, or with `w0` ([L][NW], GameOps::init_words) that state in every session.
-  void state(uint32_t* base, int NW, int L, size_t cells, const uint32_t* w0) {
+  void state(uint32_t*& base, int NW, int L, size_t cells, const uint32_t* w0) {
+    buffer(base, 4, cells * NW, L);
     const size_t Gp = Spad * L, cell_bytes = static_cast<size_t>(NW) * Gp * 4;
     const int Q4 = NW / 4, R = NW % 4;
     size_t t0 = npos;
@@ -144,10 +156,10 @@ struct PlaneSet {
       t0 = tmpl.size();
       tmpl.resize(t0 + static_cast<size_t>(NW) * L);
       for (int l = 0; l < L; ++l)
-        for (int k = 0; k < NW; ++k) tmpl[t0 + restart_word_index(NW, L, l, k)] = w0[l * NW + k];
+        for (int k = 0; k < NW; ++k) tmpl[t0 + word_index(NW, L, l, k)] = w0[l * NW + k];
     }
     auto part = [&](size_t word0, int esize, size_t rows) {  // word0: the part's first word per column
-      fill(base + word0 * Gp, esize, rows, L, 0);
+      plane(base + word0 * Gp, esize, rows, L, 0);
       planes.back().groups = static_cast<uint32_t>(cells);
       planes.back().group_stride = cell_bytes;
       if (w0) {
@@ -169,7 +181,7 @@ struct PlaneSet {
 // The selected sessions on their way to the device without a host synchronisation: two pinned
 // staging slots, each written again only once the copy that read it has completed (an event per
 // slot; the host waits only when it is two restarts ahead of the device), and one device list,
-// which the stream orders between the kernels that read it.
+// which the stream orders between the kernels that read it.  Made by the first upload, through `res`.
 struct RestartIndex {
   int32_t* host[2] = {nullptr, nullptr};  // [capacity] each, pinned
   int32_t* dev = nullptr;                 // [capacity]
@@ -177,18 +189,15 @@ struct RestartIndex {
   bool armed[2] = {false, false};  // done[k] has been recorded
   int next = 0;
 
-  hipError_t upload(const std::vector<int32_t>& idx, size_t capacity, hipStream_t stream) {
+  hipError_t upload(DeviceOwner& res, const std::vector<int32_t>& idx, size_t capacity, hipStream_t stream) {
     hipError_t e = hipSuccess;
-    if (!dev) {
-      e = hipMalloc(&dev, capacity * 4);
+    if (!done[1]) {  // (a partial failure is made again from its first missing piece)
+      if (!dev) e = res.alloc(dev, capacity * 4);
       for (int k = 0; k < 2 && e == hipSuccess; ++k) {
-        e = hipHostMalloc(&host[k], capacity * 4);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&done[k], hipEventDisableTiming);
+        if (!host[k]) e = res.alloc_host(host[k], capacity * 4);
+        if (e == hipSuccess && !done[k]) e = res.event(done[k], hipEventDisableTiming);
       }
-      if (e != hipSuccess) {
-        release();
-        return e;
-      }
+      if (e != hipSuccess) return e;
     }
     const int k = next;
     if (armed[k] && (e = hipEventSynchronize(done[k])) != hipSuccess) return e;
@@ -198,17 +207,6 @@ struct RestartIndex {
     armed[k] = true;
     next = k ^ 1;
     return hipSuccess;
-  }
-  void release() {
-    for (int k = 0; k < 2; ++k) {
-      if (done[k]) (void)hipEventDestroy(done[k]);
-      if (host[k]) (void)hipHostFree(host[k]);
-      done[k] = nullptr;
-      host[k] = nullptr;
-      armed[k] = false;
-    }
-    if (dev) (void)hipFree(dev);
-    dev = nullptr;
   }
 };
 

@@ -47,6 +47,20 @@ struct RecordLayout {
   uint64_t fingerprint = 0;
 };
 
+// The state planes' layout, for `cols` lane columns: a column's NW words lie in groups of four
+// (16-byte elements), then a pair (8 bytes), then a single word.  Word k of column c.  The same
+// function gives the layout of a one-session batch, the form a live state's template is kept in.
+inline size_t word_index(int NW, size_t cols, size_t c, int k) {
+  const int Q4 = NW / 4, R = NW % 4;
+  if (k < Q4 * 4) return static_cast<size_t>(k / 4) * 4 * cols + c * 4 + (k % 4);
+  size_t b = static_cast<size_t>(Q4) * 4 * cols;
+  if (R >= 2) {
+    if (k < Q4 * 4 + 2) return b + c * 2 + (k - Q4 * 4);
+    b += 2 * cols;
+  }
+  return b + c;
+}
+
 inline uint64_t record_hash_word(uint64_t h, uint32_t w) {  // FNV-1a, a byte at a time
   for (int i = 0; i < 4; ++i) {
     h ^= (w >> (8 * i)) & 0xffu;

@@ -600,3 +600,51 @@ def test_prepared_ticks_same_as_run_ticks(gpu_available):
             sess.prepare_ticks(dev[0:0])
     with pytest.raises(G.InvalidRequest):  # torch's current stream is not the batch stream
         sess.prepare_ticks(dev[0:1])
+
+
+def check_launch_clock_slots(read, handle, launches):
+    """rb_launch_clock_read / rb_p2p_launch_clock_read after `launches` launches on one stream: that
+    many slots, every start stamped, no end before its start, and no launch starting before the
+    one before it ended (a slot holds its own launch's stamps only)."""
+    out = (ctypes.c_uint64 * (2 * launches))()
+    n = ctypes.c_int32()
+    assert read(handle, out, launches, ctypes.byref(n)) == 0
+    assert n.value == launches
+    start, end = [out[2 * k] for k in range(launches)], [out[2 * k + 1] for k in range(launches)]
+    assert all(s != 0 for s in start), start
+    assert all(e >= s for s, e in zip(start, end)), (start, end)
+    assert all(start[k + 1] >= end[k] for k in range(launches - 1)), (start, end)
+
+
+@pytest.mark.parametrize("game,P", [(G.Game.STUB, 2), (G.Game.EX_GAME, 2)])
+def test_launch_clock_slot_holds_every_wave_of_the_grid(gpu_available, game, P):
+    """64 sessions at block 256: one workgroup of four waves runs, of which one (the stub: a lane per
+    session) or two (ex_game: a lane per player) hold sessions.  Every wave stores a start stamp, so
+    a slot holds launch_waves() of the grid (host_batch.hpp); three one-tick fused launches fill three
+    slots that do not overlap, and the armed batch computes what an unarmed twin does."""
+    import torch
+    S, cd, warm, L = 64, 2, 6, 3
+    mask, dtype = (0xFFFFFFFF, np.uint32) if game == G.Game.STUB else (0x0F, np.uint8)
+    dev = torch.from_numpy(synth_inputs(S, P, warm + L, seed=5, mask=mask, dtype=dtype)).cuda()
+    armed, _ = make_pair(game, S, P, 8, cd, 0)
+    twin, _ = make_pair(game, S, P, 8, cd, 0)
+    for sess in (armed, twin):
+        assert sess.run_ticks(dev[:warm]) == warm  # past the start-up ticks: every later call is one fused launch
+    armed.launch_clock_arm(L)
+    for sess in (armed, twin):
+        for t in range(warm, warm + L):
+            assert sess.run_ticks(dev[t:t + 1]) == 1
+    check_launch_clock_slots(armed._lib.rb_launch_clock_read, armed._h, L)
+    for a, b in zip(armed.read_live(), twin.read_live()):
+        np.testing.assert_array_equal(a, b)
+    compared = 0
+    for f in range(warm + L - 8, warm + L + 1):  # every frame the snapshot ring still holds
+        try:
+            cell = armed.read_cell(f)
+        except G.InvalidRequest:
+            continue
+        for a, b in zip(cell, twin.read_cell(f)):
+            np.testing.assert_array_equal(a, b, err_msg=f"cell {f}")
+        compared += 1
+    assert compared >= cd
+    assert (armed.mismatches() == G.NULL_FRAME).all() and (twin.mismatches() == G.NULL_FRAME).all()

@@ -698,3 +698,47 @@ def test_gpu_disconnect_at_the_current_frame_asserts_like_reference(gpu_availabl
     st, lf, na, _ = sess.status()
     assert st[0] == RB_PANIC
     assert st[1] == 0 and lf[1] == 3 and na[1] == 2
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("fanout", [False, True], ids=["plain", "fanout-always"])
+def test_gpu_p2p_launch_clock_slot_holds_every_wave_of_the_grid(gpu_available, fanout):
+    """ex_game, two players, 64 sessions at block 256: 128 lanes hold sessions, one workgroup of
+    four waves runs, and every wave stores a start stamp.  A slot holds launch_waves() of the batch's
+    widest launch (host_batch.hpp; with the fan-out fanout_kernel's 16 branches per lane), so three
+    one-tick launches fill three slots that do not overlap, and the armed batch computes what an
+    unarmed twin does."""
+    import ctypes
+
+    import torch
+    game, S, P, W, d, rd, mask, L = G.Game.EX_GAME, 64, 2, 8, 1, 1, 0b01, 3
+    inputs, upto, rin = synth_network(S, P, L, mask, rd, 1, 4)
+    di, du, dr = (torch.from_numpy(a).cuda() for a in (inputs, upto, rin))
+
+    def make():
+        b = (G.SessionBuilder(game, num_sessions=S).with_num_players(P).with_max_prediction_window(W)
+             .with_input_delay(d).with_remote_input_delay(rd).with_speculative_fanout(fanout, adaptive=False, per_player=False))
+        for h in range(P):
+            b.add_player(PlayerType.Local if (mask >> h) & 1 else PlayerType.Remote, h)
+        return b.start_p2p_session()
+
+    armed, twin = make(), make()
+    armed.launch_clock_arm(L)
+    for sess in (armed, twin):
+        for t in range(L):
+            sess.run_ticks(di[t:t + 1], du[t:t + 1], dr)
+    out = (ctypes.c_uint64 * (2 * L))()
+    n = ctypes.c_int32()
+    assert armed._lib.rb_p2p_launch_clock_read(armed._h, out, L, ctypes.byref(n)) == 0
+    assert n.value == L  # three slots
+    start, end = [out[2 * k] for k in range(L)], [out[2 * k + 1] for k in range(L)]
+    assert all(s != 0 for s in start), start
+    assert all(e >= s for s, e in zip(start, end)), (start, end)
+    # launches on one stream run in order: a slot that took only its own launch's stamps starts after the one before ended
+    assert all(start[k + 1] >= end[k] for k in range(L - 1)), (start, end)
+    np.testing.assert_array_equal(armed.read_live(), twin.read_live())
+    for a, b in zip(armed.read_cells(), twin.read_cells()):
+        np.testing.assert_array_equal(a, b)
+    for a, b in zip(armed.status() + armed.frames(), twin.status() + twin.frames()):
+        np.testing.assert_array_equal(a, b)
+    assert armed.counters() == twin.counters() and armed.totals() == twin.totals()
