@@ -15,6 +15,7 @@ LIB_PATH = os.environ.get("GGRS_AMD_LIB") or os.path.join(_HERE, "libggrs_amd.so
 
 RB_ABI_VERSION = 1
 RB_NULL_FRAME = -1
+RB_INPUT_QUEUE_LENGTH = 128  # input_queue.rs:6
 
 # rb_status
 RB_OK = 0
@@ -176,6 +177,8 @@ SIGNATURES = [
     ("rb_p2p_receive_peer_connect_status", _I32, [_P, _I32, _P, _P]),
     ("rb_p2p_export_confirmed_inputs", _I32, [_P, _P, _I32, _P, _P, _P]),
     ("rb_p2p_read_export_status", _I32, [_P, _P, _P]),
+    ("rb_p2p_set_delivery_ring", _I32, [_P, _I32]),
+    ("rb_p2p_export_local_inputs", _I32, [_P, _P, _I32, _P]),
     ("rb_p2p_time_sync_enable", _I32, [_P, _I32]),
     ("rb_p2p_receive_quality", _I32, [_P, _I32, _P, _P]),
     ("rb_p2p_export_time_sync", _I32, [_P, _P, _P]),
@@ -202,6 +205,7 @@ SIGNATURES = [
     ("rb_spectator_import_sessions", _I32, [_P, _P, _I32, _P]),
     ("rb_spectator_import_refused", _I32, [_P, _P]),
     ("rb_spectator_run_ticks", _I32, [_P, _I32, _P, _P, _I32]),
+    ("rb_spectator_set_delivery_ring", _I32, [_P, _I32]),
     ("rb_spectator_read_status", _I32, [_P, _P, _P]),
     ("rb_spectator_read_frames", _I32, [_P, _P, _P]),
     ("rb_spectator_read_live", _I32, [_P, _P, _P]),

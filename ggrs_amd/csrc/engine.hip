@@ -46,6 +46,7 @@ struct Plugin {
   void* handle;
   GameOps* (*make)(int32_t, int32_t);
   bool tick_log;  // rb_plugin_tick_log: its P2P kernels write the time-sync tick log
+  bool delivery_ring;  // rb_plugin_delivery_ring: its kernels apply the delivery ring's frame masks
 };
 std::mutex g_plugins_mu;
 std::vector<Plugin> g_plugins;
@@ -62,6 +63,11 @@ bool plugin_writes_tick_log(int game) {
   std::lock_guard<std::mutex> lk(g_plugins_mu);
   const int k = game - RB_GAME_PLUGIN_BASE;
   return k >= 0 && k < static_cast<int>(g_plugins.size()) && g_plugins[static_cast<size_t>(k)].tick_log;
+}
+bool plugin_masks_delivery_frames(int game) {
+  std::lock_guard<std::mutex> lk(g_plugins_mu);
+  const int k = game - RB_GAME_PLUGIN_BASE;
+  return k >= 0 && k < static_cast<int>(g_plugins.size()) && g_plugins[static_cast<size_t>(k)].delivery_ring;
 }
 }  // namespace rb
 
@@ -287,7 +293,8 @@ rb_status rb_register_game_plugin(const char* path, int32_t* game_id) {
     return fail(nullptr, RB_INVALID_REQUEST, "not a game plugin of this engine (rb_plugin_abi / rb_plugin_make_ops)");
   }
   auto tick_log = reinterpret_cast<int32_t (*)()>(dlsym(h, "rb_plugin_tick_log"));
-  g_plugins.push_back(Plugin{path, h, make, tick_log && tick_log() == 1});
+  auto ring = reinterpret_cast<int32_t (*)()>(dlsym(h, "rb_plugin_delivery_ring"));
+  g_plugins.push_back(Plugin{path, h, make, tick_log && tick_log() == 1, ring && ring() == 1});
   *game_id = RB_GAME_PLUGIN_BASE + static_cast<int32_t>(g_plugins.size() - 1);
   return RB_OK;
 }

@@ -1072,6 +1072,8 @@ std::unique_ptr<GameOps> make_stub_ops(int game, int players);
 std::unique_ptr<GameOps> make_plugin_ops(int game, int players);
 // whether that plugin's P2P kernels write the time-sync tick log (built since P2PParams::tick_log)
 bool plugin_writes_tick_log(int game);
+// whether that plugin's kernels apply the delivery ring's frame masks (built since P2PParams::remote_mask)
+bool plugin_masks_delivery_frames(int game);
 
 inline std::unique_ptr<GameOps> make_game(int game, int players, bool lane_per_session) {
   switch (game) {

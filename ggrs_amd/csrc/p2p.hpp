@@ -30,6 +30,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <cstddef>
+
 #include "games.hpp"
 #include "p2p_variant.hpp"
 #include "wire_varint.hpp"
@@ -409,13 +411,18 @@ struct P2PParams {
   int64_t local_stride;
   const int32_t* upto;      // tick t, handle h: upto[t * upto_stride + h * S + s]
   int64_t upto_stride;
-  const uint8_t* remote_in;  // frame f, handle h: remote_in + ((f * P + h) * S + s) * IB
+  const uint8_t* remote_in;  // frame f, handle h: remote_in + (((f & remote_mask) * P + h) * S + s) * IB
+  // linear delivery tensor: the frames it holds; a delivery ring (rb_p2p_set_delivery_ring): INT32_MAX
   int32_t remote_frames;
   int32_t S, Spad, W, delay, remote_delay, T;
   uint32_t local_mask;
   int32_t sparse;
   int32_t sync_ticks;  // 1: lock-step ticks on the plain path too (no kAsync; A/B and tests)
   int32_t many_waves;  // the batch puts more than two waves on a SIMD of this device (many_waves_per_simd)
+  // linear delivery tensor: all ones below the sign bit; a delivery ring of R frames: R - 1.  It
+  // stands in what was the four bytes of padding before `ds`, so every other field keeps its offset
+  // (the asserts below the struct) and a plug-in built before it reads them where they were.
+  int32_t remote_mask;
   DesyncParams ds;
   PeerParams peer;
   // kWire (rb_p2p_run_ticks_packets): the remote inputs arrive as the peers'
@@ -438,6 +445,12 @@ struct P2PParams {
   int32_t* acks;       // [P][S] after the launch: the newest frame received per endpoint (the ack), or null
   unsigned long long* launch_clock;  // rb_p2p_launch_clock_arm: this launch's [waves][start, end], or null
 };
+// The layout plug-ins of RB_PLUGIN_ABI 8 were built against: remote_mask took the padding before
+// `ds` and moved nothing.
+static_assert(offsetof(P2PParams, remote_frames) == 168 && offsetof(P2PParams, S) == 172 &&
+                  offsetof(P2PParams, many_waves) == 208 && offsetof(P2PParams, remote_mask) == 212 &&
+                  offsetof(P2PParams, ds) == 216 && offsetof(P2PParams, packets) == 360 && sizeof(P2PParams) == 416,
+              "P2PParams changed layout: bump RB_PLUGIN_ABI (include/ggrs_amd_game.hpp)");
 
 // The cells as check_checksum_send_interval sees them.  It runs inside
 // advance_frame, before the user executes the requests that advance_frame
@@ -1001,7 +1014,7 @@ p2p_kernel(const P2PParams p) {
     rbase[j] = kWire ? nullptr : p.remote_in + (static_cast<size_t>(min(player_of(j), P - 1)) * p.S + s) * IB;
   auto load_remote = [&](int j, int32_t f) __attribute__((always_inline)) -> uint32_t {
     if constexpr (kWire) return 0u;
-    f = max(0, min(f, p.remote_frames - 1));
+    f = max(0, min(f, p.remote_frames - 1)) & p.remote_mask;
     const uint8_t* src = rbase[j] + static_cast<uint64_t>(static_cast<uint32_t>(f)) * rstride;
     return IB == 4 ? *reinterpret_cast<const uint32_t*>(src) : *src;
   };

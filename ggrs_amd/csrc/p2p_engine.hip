@@ -56,6 +56,7 @@ struct rb_p2p {
   int32_t ts_log_ticks = 0;
   PaceParams pace{};                  // rb_p2p_run_ticks_paced / rb_p2p_pace: the status view, parked ticks, the pacer's accumulator
   bool ticked = false;                // a tick has run (rb_p2p_time_sync_enable comes before the first)
+  int32_t ring_frames = 0;            // rb_p2p_set_delivery_ring: R, or 0 for linear by-frame tensors (host state only)
   DeviceOwner res;                    // every device buffer, pinned buffer and event of the batch
   bool prof = false;
   EventPool prof_ev{res};
@@ -192,8 +193,9 @@ __global__ void p2p_peer_status_kernel(PeerParams pp, const int32_t* __restrict_
 template <int IB>
 __global__ void p2p_export_kernel(const int32_t* __restrict__ qs, const uint8_t* __restrict__ ring,
                                   const int32_t* __restrict__ status, int32_t* __restrict__ exp_state, int S, int Spad,
-                                  int P, uint8_t* __restrict__ out, int32_t frames, int32_t* __restrict__ upto,
-                                  int32_t* __restrict__ last_frames, uint8_t* __restrict__ disconnected) {
+                                  int P, uint8_t* __restrict__ out, int32_t frames, int32_t ring_frames,
+                                  int32_t* __restrict__ upto, int32_t* __restrict__ last_frames,
+                                  uint8_t* __restrict__ disconnected) {
   const int s = blockIdx.x * blockDim.x + threadIdx.x;
   if (s >= S) return;
   const size_t sp = static_cast<size_t>(Spad);
@@ -217,11 +219,15 @@ __global__ void p2p_export_kernel(const int32_t* __restrict__ qs, const uint8_t*
   // a slot the session still had to send was overwritten: frame `next` shares its slot with
   // next + 128.  Sticky, and a word of its own (the panic word and the ticks are untouched).
   if (newest != kNullFrame && newest - next >= kQueueLen) est = RB_P2P_EXPORT_OVERRUN;
+  // linear: frames below `frames`; a delivery ring of R frames: frame `next` in slot next & (R - 1),
+  // at most R frames a call (a slot is written once), the rest in the next call
+  const int32_t mask = ring_frames ? ring_frames - 1 : INT32_MAX;
+  const int32_t stop = !ring_frames ? frames : next > INT32_MAX - ring_frames ? INT32_MAX : next + ring_frames;
   if (est == RB_P2P_EXPORT_OK && status[s] != kP2PStatusPanic) {
-    while (next <= confirmed && next < frames) {
+    while (next <= confirmed && next < stop) {
       for (int h = 0; h < P; ++h) {
         const size_t src = (static_cast<size_t>(next & (kQueueLen - 1)) * P + h) * sp + s;
-        const size_t dst = (static_cast<size_t>(next) * P + h) * S + s;
+        const size_t dst = (static_cast<size_t>(next & mask) * P + h) * S + s;
         const bool blank = disc[h] && conn[h] < next;  // PlayerInput::blank_input (sync_layer.rs:210-211)
         if constexpr (IB == 4) reinterpret_cast<uint32_t*>(out)[dst] = blank ? 0u : reinterpret_cast<const uint32_t*>(ring)[src];
         else out[dst] = blank ? uint8_t{0} : ring[src];
@@ -235,6 +241,48 @@ __global__ void p2p_export_kernel(const int32_t* __restrict__ qs, const uint8_t*
   for (int h = 0; h < P; ++h) {  // local_connect_status: the Input message's peer_connect_status
     last_frames[static_cast<size_t>(h) * S + s] = conn[h];
     disconnected[static_cast<size_t>(h) * S + s] = disc[h] ? 1 : 0;
+  }
+}
+
+// UdpProtocol::send_input (protocol.rs:439-466) as P2PSession::add_local_input calls it for every
+// remote endpoint (p2p_session.rs:330-353), in tensor form: one thread per session, the local
+// handles' inputs of the frames after sent[h][s] up to local_connect_status[h].last_frame from the
+// input ring into the caller's by-frame tensor (include/ggrs_amd.h rb_p2p_export_local_inputs).
+// ring_frames: 0 for a linear tensor of `frames` frames, R for a delivery ring (frames == R), whose
+// slot is the frame & (R - 1).
+template <int IB>
+__global__ void p2p_export_local_kernel(const int32_t* __restrict__ qs, const uint8_t* __restrict__ ring,
+                                        const int32_t* __restrict__ status, int S, int Spad, int P, uint32_t local_mask,
+                                        uint8_t* __restrict__ out, int32_t frames, int32_t ring_frames,
+                                        int32_t* __restrict__ sent) {
+  const int s = blockIdx.x * blockDim.x + threadIdx.x;
+  if (s >= S || status[s] == kP2PStatusPanic) return;
+  const size_t sp = static_cast<size_t>(Spad);
+  const int32_t cur = qs[QS_CUR * sp + s];
+  const int32_t mask = ring_frames ? ring_frames - 1 : INT32_MAX;
+  for (int h = 0; h < P; ++h) {
+    if (!((local_mask >> h) & 1u)) continue;
+    uint32_t w[4];
+    int32_t ab[7] = {0, 0, 0, 0, 0, 0, 0};
+    for (int i = 0; i < 4; ++i) w[i] = static_cast<uint32_t>(qs[(QS_PLAYER0 + (QF_LA_CONN + i) * 4 + h) * sp + s]);
+    if (w[3] & kQmEsc)
+      for (int i = 0; i < 7; ++i) ab[i] = qs[(QS_PLAYER0 + (QF_ABS0 + i) * 4 + h) * sp + s];
+    const QFields f = q_unpack(w, cur, ab);
+    // the newest frame the tensor can hold: all of them in a ring (its slots are reused)
+    const int32_t last = ring_frames ? f.conn : min(f.conn, frames - 1);
+    const int32_t done = sent[static_cast<size_t>(h) * S + s];
+    if (last == kNullFrame || done >= last) continue;
+    // the 128-entry input ring holds frames last_frame - 127 .. last_frame: older ones are lost
+    // (the ring's R >= 128, so one call never writes a slot twice)
+    int32_t fr = max(max(done, kNullFrame) + 1, f.conn - (kQueueLen - 1));
+    if (fr > last) continue;  // (a linear tensor more than 127 frames short of last_frame)
+    for (; fr <= last; ++fr) {
+      const size_t src = (static_cast<size_t>(fr & (kQueueLen - 1)) * P + h) * sp + s;
+      const size_t dst = (static_cast<size_t>(fr & mask) * P + h) * S + s;
+      if constexpr (IB == 4) reinterpret_cast<uint32_t*>(out)[dst] = reinterpret_cast<const uint32_t*>(ring)[src];
+      else out[dst] = ring[src];
+    }
+    sent[static_cast<size_t>(h) * S + s] = last;
   }
 }
 
@@ -644,6 +692,8 @@ rb_status fan_after(rb_p2p* b, int32_t n) {
 
 namespace {
 constexpr const char* kTsOff = "time sync is off (rb_p2p_time_sync_enable)";
+constexpr const char* kRingFrames =
+    "the batch has a delivery ring (rb_p2p_set_delivery_ring): the by-frame tensor holds exactly ring_frames frames";
 // The tick log for a call of n ticks.  It grows to the largest call seen, and only once the stream
 // is idle: the launches before this call may still read the old one.
 rb_status ts_log_reserve(rb_p2p* b, int32_t n) {
@@ -679,7 +729,9 @@ rb_status tick_params(rb_p2p* b, int32_t T, const void* local_inputs, int64_t lo
   p.upto = remote_upto;
   p.upto_stride = static_cast<int64_t>(b->P) * b->S;
   p.remote_in = static_cast<const uint8_t*>(remote_inputs);
-  p.remote_frames = remote_frames;
+  // a delivery ring: no frame is clamped to the tensor's length, frame f sits in slot f & (R - 1)
+  p.remote_frames = b->ring_frames ? INT32_MAX : remote_frames;
+  p.remote_mask = b->ring_frames ? b->ring_frames - 1 : INT32_MAX;
   p.T = T;
   if (b->ts_on) {
     rb_status r = ts_log_reserve(b, log_ticks);
@@ -707,6 +759,7 @@ rb_status rb_p2p_run_ticks(rb_p2p* b, int32_t n_ticks, const void* local_inputs,
   if (n_ticks <= 0) return RB_OK;
   if (!local_inputs || !remote_upto || !remote_inputs || remote_frames <= 0)
     return fail(b, RB_INVALID_REQUEST, "rb_p2p_run_ticks: missing input tensor");
+  if (b->ring_frames && remote_frames != b->ring_frames) return fail(b, RB_INVALID_REQUEST, kRingFrames);
   DeviceScope dev_scope(b->device);
   P2PParams p;
   LaunchEv ev;
@@ -756,6 +809,7 @@ rb_status rb_p2p_run_ticks_paced(rb_p2p* b, int32_t n_ticks, const void* local_i
   if (n_ticks <= 0) return RB_OK;
   if (!local_inputs || !remote_upto || !remote_inputs || remote_frames <= 0)
     return fail(b, RB_INVALID_REQUEST, "rb_p2p_run_ticks_paced: missing input tensor");
+  if (b->ring_frames && remote_frames != b->ring_frames) return fail(b, RB_INVALID_REQUEST, kRingFrames);
   if (b->fanout)  // the move-to-front rows and branch validity under a parked poll: a later step
     return fail(b, RB_INVALID_REQUEST, "rb_p2p_run_ticks_paced: a batch with the fan-out takes rb_p2p_run_ticks");
   const int IB = b->ops->input_bytes;
@@ -782,8 +836,8 @@ rb_status rb_p2p_run_ticks_paced(rb_p2p* b, int32_t n_ticks, const void* local_i
     p.local_in = static_cast<const uint8_t*>(local_inputs) + static_cast<int64_t>(t) * local_stride;
     p.upto = remote_upto + static_cast<int64_t>(t) * p.upto_stride;
     hipLaunchKernelGGL(poll, grid, block, 0, b->stream, b->pace, mask, b->qs, static_cast<uint8_t*>(b->ring), b->status,
-                       b->counters, p.upto, p.remote_in, remote_frames, b->cfg.remote_delay, b->cfg.local_mask, ts, b->S,
-                       b->Spad);
+                       b->counters, p.upto, p.remote_in, p.remote_frames, p.remote_mask, b->cfg.remote_delay,
+                       b->cfg.local_mask, ts, b->S, b->Spad);
     RB_TRY(b, hipGetLastError());
     p.launch_clock = b->clock.next();
     const hipError_t e = b->ops->launch_p2p(p, b->block, b->stream);
@@ -1111,6 +1165,7 @@ rb_status rb_p2p_export_confirmed_inputs(rb_p2p* b, void* inputs_by_frame, int32
                                          int32_t* last_frames, uint8_t* disconnected) {
   if (!inputs_by_frame || !upto || !last_frames || !disconnected || frames <= 0)
     return fail(b, RB_INVALID_REQUEST, "rb_p2p_export_confirmed_inputs: missing output tensor");
+  if (b->ring_frames && frames != b->ring_frames) return fail(b, RB_INVALID_REQUEST, kRingFrames);
   DeviceScope dev_scope(b->device);
   if (rb_status r = export_reserve(b); r != RB_OK) return r;
   const dim3 grid((b->S + 255) / 256), block(256);
@@ -1118,7 +1173,32 @@ rb_status rb_p2p_export_confirmed_inputs(rb_p2p* b, void* inputs_by_frame, int32
   if (b->ops->input_bytes != 4 && b->ops->input_bytes != 1)
     return fail(b, RB_INVALID_REQUEST, "rb_p2p_export_confirmed_inputs: 1- and 4-byte inputs");
   hipLaunchKernelGGL(k, grid, block, 0, b->stream, b->qs, static_cast<const uint8_t*>(b->ring), b->status, b->exp_state,
-                     b->S, b->Spad, b->P, static_cast<uint8_t*>(inputs_by_frame), frames, upto, last_frames, disconnected);
+                     b->S, b->Spad, b->P, static_cast<uint8_t*>(inputs_by_frame), frames, b->ring_frames, upto, last_frames,
+                     disconnected);
+  RB_TRY(b, hipGetLastError());
+  return RB_OK;
+}
+
+rb_status rb_p2p_set_delivery_ring(rb_p2p* b, int32_t ring_frames) {
+  if (ring_frames != 0 && (ring_frames < RB_INPUT_QUEUE_LENGTH || (ring_frames & (ring_frames - 1)) != 0))
+    return fail(b, RB_INVALID_REQUEST, "rb_p2p_set_delivery_ring: ring_frames is 0 or a power of two of at least 128");
+  if (ring_frames != 0 && b->cfg.game >= RB_GAME_PLUGIN_BASE && !plugin_masks_delivery_frames(b->cfg.game))
+    return fail(b, RB_INVALID_REQUEST, "rb_p2p_set_delivery_ring: rebuild the game plugin against the current headers");
+  b->ring_frames = ring_frames;
+  return RB_OK;
+}
+
+rb_status rb_p2p_export_local_inputs(rb_p2p* b, void* inputs_by_frame, int32_t frames, int32_t* sent) {
+  if (!inputs_by_frame || !sent || frames <= 0)
+    return fail(b, RB_INVALID_REQUEST, "rb_p2p_export_local_inputs: missing tensor");
+  if (b->ring_frames && frames != b->ring_frames) return fail(b, RB_INVALID_REQUEST, kRingFrames);
+  if (b->ops->input_bytes != 4 && b->ops->input_bytes != 1)
+    return fail(b, RB_INVALID_REQUEST, "rb_p2p_export_local_inputs: 1- and 4-byte inputs");
+  DeviceScope dev_scope(b->device);
+  const dim3 grid((b->S + 255) / 256), block(256);
+  auto k = b->ops->input_bytes == 4 ? p2p_export_local_kernel<4> : p2p_export_local_kernel<1>;
+  hipLaunchKernelGGL(k, grid, block, 0, b->stream, b->qs, static_cast<const uint8_t*>(b->ring), b->status, b->S, b->Spad,
+                     b->P, b->cfg.local_mask, static_cast<uint8_t*>(inputs_by_frame), frames, b->ring_frames, sent);
   RB_TRY(b, hipGetLastError());
   return RB_OK;
 }

@@ -52,7 +52,7 @@ template <int IB, int P>
 __global__ void __launch_bounds__(256)
 p2p_poll_kernel(const PaceParams pc, const uint8_t* __restrict__ run_mask, int32_t* __restrict__ qs, uint8_t* __restrict__ ring,
                 int32_t* __restrict__ status, uint32_t* __restrict__ counters, const int32_t* __restrict__ upto,
-                const uint8_t* __restrict__ remote_in, int32_t remote_frames, int32_t remote_delay, uint32_t local_mask,
+                const uint8_t* __restrict__ remote_in, int32_t remote_frames, int32_t remote_mask, int32_t remote_delay, uint32_t local_mask,
                 const TimeSyncParams ts, int S, int Spad) {
   const int s = blockIdx.x * blockDim.x + threadIdx.x;
   if (s >= S) return;
@@ -100,7 +100,7 @@ p2p_poll_kernel(const PaceParams pc, const uint8_t* __restrict__ run_mask, int32
     int32_t fr = q.conn_last == kNullFrame ? remote_delay : q.conn_last + 1;
     if (fr > end) continue;  // nothing new: the rows stay as they are
     for (; fr <= end; ++fr) {
-      const uint8_t* src = rbase + static_cast<uint64_t>(static_cast<uint32_t>(max(fr, 0))) * rstride;
+      const uint8_t* src = rbase + static_cast<uint64_t>(static_cast<uint32_t>(max(fr, 0) & remote_mask)) * rstride;
       const uint32_t v = IB == 4 ? *reinterpret_cast<const uint32_t*>(src) : *src;
       q_add<PollNoCanon>(q, io, h, static_cast<unsigned>(s), fr, v);  // add_remote_input (frame delay 0)
       q.conn_last = fr;

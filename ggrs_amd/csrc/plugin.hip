@@ -26,6 +26,11 @@ int32_t rb_plugin_players() { return RB_PLUGIN_GAME::kPlayers; }
 // before it lacks this symbol and the engine refuses rb_p2p_time_sync_enable for its game.
 int32_t rb_plugin_tick_log() { return 1; }
 
+// The plugin's P2P and spectator kernels apply the delivery ring's frame masks (P2PParams::remote_mask,
+// SpectatorParams::in_mask); a plugin built before them lacks this symbol and the engine refuses a
+// delivery ring for its game (the linear layout runs as before).
+int32_t rb_plugin_delivery_ring() { return 1; }
+
 // A new GameOps for `players` (must be the game's kPlayers), owned by the caller
 // (deleted through its virtual destructor); NULL on a mismatch.
 rb::GameOps* rb_plugin_make_ops(int32_t players, int32_t abi) {

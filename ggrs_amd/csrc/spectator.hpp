@@ -43,6 +43,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <cstddef>
+
 #include "games.hpp"
 
 namespace rb {
@@ -61,11 +63,19 @@ struct SpectatorParams {
   unsigned long long* stats;
   uint32_t* counters;        // [1]: unexpected math paths (the games' advance reports them)
   const int32_t* upto;       // tick t: upto[t * S + s], the newest frame delivered before the tick
-  const uint8_t* in;         // frame f, player h: in + ((f * P + h) * S + s) * IB
-  int32_t in_frames;         // frames the tensor holds; a delivery mark past them counts as in_frames - 1
+  const uint8_t* in;         // frame f, player h: in + (((f & in_mask) * P + h) * S + s) * IB
+  // linear tensor: the frames it holds (a delivery mark past them counts as in_frames - 1); a
+  // delivery ring (rb_spectator_set_delivery_ring): INT32_MAX, no frame is clamped
+  int32_t in_frames;
   int32_t S, Spad, T;
   int32_t max_behind, catchup;  // 1 <= catchup < max_behind < kSpectatorBuffer
+  // linear: all ones below the sign bit; a delivery ring of R frames: R - 1, frame f in slot
+  // f & in_mask.  The last field: a plug-in built before it reads the fields above where they were.
+  int32_t in_mask;
 };
+static_assert(offsetof(SpectatorParams, in_frames) == 80 && offsetof(SpectatorParams, S) == 84 &&
+                  offsetof(SpectatorParams, catchup) == 100 && offsetof(SpectatorParams, in_mask) == 104,
+              "SpectatorParams changed layout: bump RB_PLUGIN_ABI (include/ggrs_amd_game.hpp)");
 
 // One launch = T ticks of SpectatorSession::advance_frame for every session.
 // The game words stay in registers across the ticks.  Catch-up differs per
@@ -106,7 +116,7 @@ __global__ void __launch_bounds__(256) spectator_kernel(const SpectatorParams p)
   const uint32_t istride = static_cast<uint32_t>(P) * static_cast<uint32_t>(p.S) * IB;
   const int32_t last_in = p.in_frames - 1;
   auto load_in = [&](int j, int32_t f) __attribute__((always_inline)) -> uint32_t {
-    f = max(0, min(f, last_in));  // always a valid address; a frame past last_recv is loaded and never used
+    f = max(0, min(f, last_in)) & p.in_mask;  // always a valid address; a frame past last_recv is loaded and never used
     const uint8_t* src = ibase[j] + static_cast<uint64_t>(static_cast<uint32_t>(f)) * istride;
     return IB == 4 ? *reinterpret_cast<const uint32_t*>(src) : *src;
   };

@@ -28,6 +28,7 @@ struct rb_spectator {
   RestartIndex restart_idx;             // rb_spectator_restart_sessions' selected sessions
   RestartIndex move_idx;                // rb_spectator_export_sessions' / rb_spectator_import_sessions'
   uint32_t* refused = nullptr;          // [1] records rb_spectator_import_sessions refused since create
+  int32_t ring_frames = 0;              // rb_spectator_set_delivery_ring: R, or 0 for a linear host_inputs (host state only)
   DeviceOwner res;                      // everything above that lies on the device
   std::string last_err;
 
@@ -213,6 +214,9 @@ rb_status rb_spectator_run_ticks(rb_spectator* b, int32_t n_ticks, const int32_t
   if (n_ticks <= 0) return RB_OK;
   if (!host_upto || !host_inputs || frames <= 0)
     return fail(b, RB_INVALID_REQUEST, "rb_spectator_run_ticks: missing input tensor");
+  if (b->ring_frames && frames != b->ring_frames)
+    return fail(b, RB_INVALID_REQUEST,
+                "the batch has a delivery ring (rb_spectator_set_delivery_ring): host_inputs holds exactly ring_frames frames");
   SpectatorParams p{};
   p.live = b->live;
   p.cs = b->cs;
@@ -224,7 +228,9 @@ rb_status rb_spectator_run_ticks(rb_spectator* b, int32_t n_ticks, const int32_t
   p.counters = b->counters;
   p.upto = host_upto;
   p.in = static_cast<const uint8_t*>(host_inputs);
-  p.in_frames = frames;
+  // a delivery ring: no frame is clamped to the tensor's length, frame f sits in slot f & (R - 1)
+  p.in_frames = b->ring_frames ? INT32_MAX : frames;
+  p.in_mask = b->ring_frames ? b->ring_frames - 1 : INT32_MAX;
   p.S = b->S;
   p.Spad = b->Spad;
   p.T = n_ticks;
@@ -233,6 +239,15 @@ rb_status rb_spectator_run_ticks(rb_spectator* b, int32_t n_ticks, const int32_t
   DeviceScope dev_scope(b->device);
   const hipError_t e = b->ops->launch_spectator(p, b->block, b->stream);
   if (e != hipSuccess) return fail(b, RB_DEVICE_ERROR, std::string("spectator launch: ") + hipGetErrorString(e));
+  return RB_OK;
+}
+
+rb_status rb_spectator_set_delivery_ring(rb_spectator* b, int32_t ring_frames) {
+  if (ring_frames != 0 && (ring_frames < RB_INPUT_QUEUE_LENGTH || (ring_frames & (ring_frames - 1)) != 0))
+    return fail(b, RB_INVALID_REQUEST, "rb_spectator_set_delivery_ring: ring_frames is 0 or a power of two of at least 128");
+  if (ring_frames != 0 && b->cfg.game >= RB_GAME_PLUGIN_BASE && !plugin_masks_delivery_frames(b->cfg.game))
+    return fail(b, RB_INVALID_REQUEST, "rb_spectator_set_delivery_ring: rebuild the game plugin against the current headers");
+  b->ring_frames = ring_frames;
   return RB_OK;
 }
 

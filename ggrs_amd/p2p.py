@@ -62,6 +62,7 @@ class P2PSession(_Movable, _StreamOrdered):
         self.state_bytes = lib.rb_p2p_state_bytes(handle)
         self.input_dtype = input_dtype(game, lib.rb_p2p_input_bytes(handle))
         self._device = int(cfg.device)
+        self.delivery_ring = 0  # set_delivery_ring: R, or 0 for linear by-frame tensors
         self._bind(self._device, lib.rb_p2p_get_stream(handle) or 0)
 
     def close(self):
@@ -109,7 +110,8 @@ class P2PSession(_Movable, _StreamOrdered):
 
         local_inputs  [T, P, S] Input values (remote handles' rows ignored)
         remote_upto   [T, P, S] int32 newest delivered frame per remote handle
-        remote_inputs [F, P, S] Input values by frame (local handles' rows ignored)
+        remote_inputs [F, P, S] Input values by frame (local handles' rows ignored); after
+                      set_delivery_ring(R) the ring [R, P, S], frame f of a session in slot f & (R - 1)
         run_mask      None, or [T, S] uint8: 0 parks session s in tick t, which then only
                       polls (rb_p2p_run_ticks_paced; T one-tick sequences on the stream)
         All torch CUDA tensors on the batch's device."""
@@ -118,6 +120,8 @@ class P2PSession(_Movable, _StreamOrdered):
         assert tuple(local_inputs.shape[1:]) == (self.num_players, self.num_sessions)
         assert tuple(remote_upto.shape) == (T, self.num_players, self.num_sessions)
         assert tuple(remote_inputs.shape[1:]) == (self.num_players, self.num_sessions)
+        assert not self.delivery_ring or int(remote_inputs.shape[0]) == self.delivery_ring, \
+            "the batch has a delivery ring: remote_inputs holds exactly its R frames"
         lp, lk = _dev_ptr(local_inputs)
         up, uk = _dev_ptr(remote_upto)
         rp, rk = _dev_ptr(remote_inputs)
@@ -352,6 +356,7 @@ class P2PSession(_Movable, _StreamOrdered):
         P, S = self.num_players, self.num_sessions
         assert tuple(inputs_by_frame.shape[1:]) == (P, S) and inputs_by_frame.is_contiguous()
         assert inputs_by_frame.element_size() == np.dtype(self.input_dtype).itemsize
+        assert not self.delivery_ring or int(inputs_by_frame.shape[0]) == self.delivery_ring
         assert tuple(upto.shape) == (S,) and upto.dtype == torch.int32 and upto.is_contiguous()
         assert tuple(last_frames.shape) == (P, S) and last_frames.dtype == torch.int32 and last_frames.is_contiguous()
         assert tuple(disconnected.shape) == (P, S) and disconnected.dtype == torch.uint8 and disconnected.is_contiguous()
@@ -360,6 +365,39 @@ class P2PSession(_Movable, _StreamOrdered):
         st = self._lib.rb_p2p_export_confirmed_inputs(self._h, ptrs[0], int(inputs_by_frame.shape[0]), ptrs[1], ptrs[2],
                                                       ptrs[3])
         self._post(cur, (inputs_by_frame, upto, last_frames, disconnected), outputs=True)
+        self._check(st)
+
+    # -- per-session delivery rings
+    def set_delivery_ring(self, ring_frames: int) -> None:
+        """Every by-frame tensor of the batch (run_ticks' remote_inputs, the inputs_by_frame of
+        export_confirmed_inputs and export_local_inputs) becomes a ring [R, P, S] indexed by each
+        session's own frame, frame f in slot f & (R - 1) (rb_p2p_set_delivery_ring): sessions of
+        one batch may then sit any number of frames apart.  R a power of two >= 128; 0 returns to
+        the linear layout.  Between run_ticks calls; no device work.  The caller keeps every frame
+        between a session's last delivered frame and the call's largest watermark in its slot
+        (``DeliveryRing``); older content of a slot is never read."""
+        self._check(self._lib.rb_p2p_set_delivery_ring(self._h, int(ring_frames)))
+        self.delivery_ring = int(ring_frames)
+
+    def export_local_inputs(self, inputs_by_frame, sent) -> None:
+        """UdpProtocol::send_input in tensor form (rb_p2p_export_local_inputs), between run_ticks
+        calls: for every local handle h the inputs of frames sent[h, s] + 1 .. the newest frame
+        add_local_input queued go to inputs_by_frame [F, P, S] (the batch's layout: linear, or the
+        delivery ring), and sent [P, S] int32 becomes the last frame written.  Remote handles'
+        rows of both tensors are untouched.  sent is the caller's: NULL_FRAME at first and after
+        restarting a session.  At most the newest 128 frames are still there; older ones are
+        skipped.  A peer batch reads the same tensor as its remote_inputs, with (an older copy
+        of) sent as its remote_upto."""
+        import torch
+        P, S = self.num_players, self.num_sessions
+        assert tuple(inputs_by_frame.shape[1:]) == (P, S) and inputs_by_frame.is_cuda and inputs_by_frame.is_contiguous()
+        assert inputs_by_frame.element_size() == np.dtype(self.input_dtype).itemsize
+        assert not self.delivery_ring or int(inputs_by_frame.shape[0]) == self.delivery_ring
+        assert tuple(sent.shape) == (P, S) and sent.dtype == torch.int32 and sent.is_cuda and sent.is_contiguous()
+        cur = self._pre()
+        st = self._lib.rb_p2p_export_local_inputs(self._h, ctypes.c_void_p(inputs_by_frame.data_ptr()),
+                                                  int(inputs_by_frame.shape[0]), ctypes.c_void_p(sent.data_ptr()))
+        self._post(cur, (inputs_by_frame, sent), outputs=True)
         self._check(st)
 
     def export_status(self):

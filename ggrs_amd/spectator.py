@@ -42,6 +42,7 @@ class SpectatorSession(_Movable, _StreamOrdered):
         self.state_bytes = lib.rb_spectator_state_bytes(handle)
         self.input_dtype = input_dtype(game, lib.rb_spectator_input_bytes(handle))
         self._device = int(cfg.device)
+        self.delivery_ring = 0  # set_delivery_ring: R, or 0 for a linear host_inputs
         self._bind(self._device, lib.rb_spectator_get_stream(handle) or 0)
 
     def close(self):
@@ -102,16 +103,27 @@ class SpectatorSession(_Movable, _StreamOrdered):
         st = self._lib.rb_spectator_restart_sessions(self._h, None if m is None else m.ctypes.data_as(ctypes.c_void_p))
         self._check(st)
 
+    def set_delivery_ring(self, ring_frames: int) -> None:
+        """host_inputs becomes a ring [R, P, S] indexed by each spectator's own frame, frame f in
+        slot f & (R - 1) (rb_spectator_set_delivery_ring): what a host batch in ring mode
+        exports.  R a power of two >= 128; 0 returns to the linear layout.  The ring's head may
+        lead the host_upto a spectator is handed by at most R - 60 frames."""
+        self._check(self._lib.rb_spectator_set_delivery_ring(self._h, int(ring_frames)))
+        self.delivery_ring = int(ring_frames)
+
     def run_ticks(self, host_upto, host_inputs) -> None:
         """T ticks of advance_frame + handle_requests in one device launch.
 
         host_upto   [T, S] int32: the newest frame delivered before each tick (NULL_FRAME: none)
         host_inputs [F, P, S] Input values by frame, complete up to the largest host_upto
+                    (after set_delivery_ring(R): the ring [R, P, S])
         Both torch CUDA tensors on the batch's device."""
         import torch
         T = int(host_upto.shape[0])
         assert tuple(host_upto.shape) == (T, self.num_sessions) and host_upto.dtype == torch.int32
         assert tuple(host_inputs.shape[1:]) == (self._num_players, self.num_sessions)
+        assert not self.delivery_ring or int(host_inputs.shape[0]) == self.delivery_ring, \
+            "the batch has a delivery ring: host_inputs holds exactly its R frames"
         assert host_inputs.element_size() == np.dtype(self.input_dtype).itemsize
         up, uk = _dev_ptr(host_upto)
         ip, ik = _dev_ptr(host_inputs)

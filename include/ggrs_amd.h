@@ -376,7 +376,10 @@ void* rb_p2p_get_stream(const rb_p2p* b);  /* as rb_get_stream */
  *   remote_upto   int32 [n_ticks][num_players][S]: newest frame delivered for
  *                 remote handle h before tick t's advance_frame (monotone;
  *                 entries of local handles ignored)
- *   remote_inputs [remote_frames][num_players][S] Input values by frame
+ *   remote_inputs [remote_frames][num_players][S] Input values by frame (a
+ *                 watermark past remote_frames - 1 counts as that), or, after
+ *                 rb_p2p_set_delivery_ring(R), the ring [R][num_players][S]
+ *                 with remote_frames == R
  * A session that hits PredictionThreshold (sync_layer.rs:163-167) does not
  * advance that tick (rb_p2p_read_status reports it), exactly as the
  * reference's advance_frame returns Err: its bookkeeping moves, its game does
@@ -602,6 +605,81 @@ rb_status rb_p2p_receive_peer_connect_status(rb_p2p* b, int32_t endpoint, const 
 #define RB_P2P_EXPORT_OVERRUN 1
 rb_status rb_p2p_export_confirmed_inputs(rb_p2p* b, void* inputs_by_frame, int32_t frames, int32_t* upto,
                                          int32_t* last_frames, uint8_t* disconnected);
+/* ---- Per-session delivery rings.  By default every
+ * by-frame tensor of a batch is linear: [frames][num_players][S], indexed by
+ * each session's absolute frame, so it must reach the frame of the batch's
+ * oldest session.  Once sessions restart (rb_p2p_restart_sessions) or arrive
+ * (rb_p2p_import_sessions) at different times no window of absolute frames
+ * serves them all.  A delivered frame is read exactly once, though:
+ * Event::Input hands it to the InputQueue (p2p_session.rs:838-852,
+ * input_queue.rs:149-204) while ConnectionStatus::last_frame < frame <=
+ * remote_upto, and from then on it lives in the batch's own 128-entry ring.
+ *
+ * rb_p2p_set_delivery_ring(b, R) makes every by-frame tensor argument of the
+ * batch a ring of R frames indexed by each session's OWN frame: [R][num_players][S],
+ * frame f of session s in slot f & (R - 1).  That is remote_inputs of
+ * rb_p2p_run_ticks and rb_p2p_run_ticks_paced and inputs_by_frame of
+ * rb_p2p_export_confirmed_inputs and rb_p2p_export_local_inputs.  The matching
+ * remote_frames / frames argument must equal R, else RB_INVALID_REQUEST (a
+ * linear tensor passed by mistake).  R == 0 returns the batch to the linear
+ * layout (the default); otherwise R is a power of two of at least
+ * RB_INPUT_QUEUE_LENGTH; anything else is RB_INVALID_REQUEST with nothing
+ * changed.  Called between tick calls; host state only: no device state, no
+ * synchronisation, session records and their fingerprints are unchanged.
+ * rb_p2p_run_ticks_packets has no by-frame tensor and ignores it.  A plug-in
+ * game built before the frame mask (no rb_plugin_delivery_ring, plugin.hip)
+ * is refused a ring, RB_INVALID_REQUEST; its linear layout runs as before.
+ *
+ * In ring mode no frame is clamped to the tensor's length: time sync's
+ * last_recv (protocol.rs:268-277) and the parked poll's are remote_upto itself.
+ *
+ * The caller's contract:
+ *   - at launch, every frame in (newest frame delivered before the call,
+ *     largest watermark of the call] is in its slot, per endpoint;
+ *   - that span is at most R frames per endpoint (a poll that adds 128 or more
+ *     frames to a non-empty queue fires input_queue.rs:181's assert anyway);
+ *   - a slot's earlier content, including a previous match's inputs in a
+ *     restarted session's column, is never read: a consumed frame is not read
+ *     again, and frames past the watermark are loaded ahead and discarded.
+ * Addresses stay inside the tensor whatever the watermarks are; a caller that
+ * breaks the contract gets the inputs its slots held, not a fault, and is not
+ * detected.
+ *
+ * rb_p2p_export_confirmed_inputs in ring mode writes frame `next` to slot
+ * next & (R - 1) and exports at most R frames per session in one call (no slot
+ * twice); the rest follows in the next call, `upto` says where it stopped.  The
+ * 128-frame overrun rule and RB_P2P_EXPORT_OVERRUN are unchanged. */
+rb_status rb_p2p_set_delivery_ring(rb_p2p* b, int32_t ring_frames);
+
+/* UdpProtocol::send_input (protocol.rs:439-466) as add_local_input calls it for
+ * every remote endpoint (p2p_session.rs:330-353), in tensor form: the feed of
+ * a peer batch, the twin of rb_p2p_export_confirmed_inputs.  Device pointers,
+ * stream ordered, called between tick calls.  For every session and every
+ * LOCAL handle h, the inputs of frames sent[h][s] + 1 ..
+ * local_connect_status[h].last_frame (the newest frame add_local_input queued:
+ * current frame - 1 + input_delay) go from the batch's InputQueue to
+ *   inputs_by_frame [frames][num_players][S] Input values, in the batch's
+ *                   current layout: linear (frames below `frames` only), or the
+ *                   delivery ring (frames == R, frame f in slot f & (R - 1))
+ * and then
+ *   sent            int32 [num_players][S] = the last frame written.
+ * Rows of remote handles, in inputs_by_frame and in sent, are untouched.  sent
+ * is the caller's state (pending_output's front, protocol.rs:462-466):
+ * RB_NULL_FRAME at first, and again once the caller restarts the session; the
+ * library keeps no plane for it.  The frames below input_delay are the blank
+ * inputs of the queue's delay fill (input_queue.rs:227-231), which the peer
+ * skips (rb_p2p_config.remote_delay).
+ * The InputQueue holds the newest 128 frames: a call never goes back further
+ * than last_frame - 127; it skips ahead, and the older frames are lost (call
+ * at least every 128 ticks).  Panicked sessions export nothing.  Inputs of 1
+ * and 4 bytes; else RB_INVALID_REQUEST.
+ *
+ * Two batches that are each other's peers can share one [R][P][S] ring and one
+ * sent tensor: each writes the rows of its own handles and reads the other's,
+ * and the caller models latency by handing each side an older copy of sent as
+ * its remote_upto. */
+rb_status rb_p2p_export_local_inputs(rb_p2p* b, void* inputs_by_frame, int32_t frames, int32_t* sent);
+
 /* Per session: RB_P2P_EXPORT_OK / RB_P2P_EXPORT_OVERRUN and next_spectator_frame
  * (both as the last export left them; before the first: OK and 0).  Either
  * pointer may be NULL.  Synchronises. */
@@ -826,9 +904,29 @@ rb_status rb_spectator_import_refused(rb_spectator* b, uint32_t* count);   /* re
  * advance (RB_PREDICTION_THRESHOLD); one whose next frame left the 60-frame
  * spectator buffer (last_recv_frame >= frame + 60) never advances again
  * (RB_SPECTATOR_TOO_FAR_BEHIND).  A player the host status reports
- * disconnected before the frame advances as (zeroed, Disconnected). */
+ * disconnected before the frame advances as (zeroed, Disconnected).
+ * With a delivery ring (rb_spectator_set_delivery_ring) host_inputs is
+ * [R][num_players][S], frames == R, host_upto is never clamped, and the ring's
+ * head may lead the host_upto handed here by at most R - 60 frames. */
 rb_status rb_spectator_run_ticks(rb_spectator* b, int32_t n_ticks, const int32_t* host_upto, const void* host_inputs,
                                  int32_t frames);
+
+/* rb_p2p_set_delivery_ring for a spectator batch: host_inputs becomes a ring
+ * [R][num_players][S] indexed by each spectator's own frame (frame f in slot
+ * f & (R - 1)), what a host batch in ring mode exports, and `frames` must equal
+ * R (else RB_INVALID_REQUEST).  R == 0: linear (the default); otherwise a power
+ * of two of at least RB_INPUT_QUEUE_LENGTH; anything else RB_INVALID_REQUEST
+ * with nothing changed.  Between tick calls, host state only.  In ring mode
+ * last_recv_frame = max(last_recv_frame, host_upto), unclamped.
+ * A spectator reads frame f when its current_frame reaches f - 1, and never
+ * once last_recv_frame >= f + 60 (inputs_at_frame,
+ * p2p_spectator_session.rs:177-187, then answers SpectatorTooFarBehind).  So
+ * at launch every frame in (current_frame, largest host_upto of the call] that
+ * is younger than host_upto - 60 must still be in its slot: the ring's head
+ * (the newest frame the host has exported into it) may lead the host_upto a
+ * spectator is handed by at most R - 60 frames.  Older content of a slot is
+ * never read. */
+rb_status rb_spectator_set_delivery_ring(rb_spectator* b, int32_t ring_frames);
 
 /* Per session, the last tick: its rb_status (RB_OK, RB_PREDICTION_THRESHOLD,
  * RB_SPECTATOR_TOO_FAR_BEHIND) and AdvanceFrame count (-1 before the first

@@ -62,7 +62,15 @@
  * with a field only packet-fed launches use, so the layout is unchanged and
  * a plug-in built before it runs as before.  Such a plug-in cannot log
  * ticks: the engine asks for rb_plugin_tick_log (plugin.hip) and refuses
- * rb_p2p_time_sync_enable for a plug-in without it. */
+ * rb_p2p_time_sync_enable for a plug-in without it.  The delivery ring's
+ * frame masks needed none either: the P2P one stands in the padding before
+ * the desync block of the P2P launch parameters and the spectators' is
+ * appended to theirs, so no other field moves (static_asserts on the offsets
+ * in p2p.hpp and spectator.hpp hold that), and in the linear
+ * layout (the default) a kernel that ignores them computes the same.  The
+ * engine asks for rb_plugin_delivery_ring and refuses
+ * rb_p2p_set_delivery_ring / rb_spectator_set_delivery_ring with a ring for a
+ * plug-in without it. */
 #define RB_PLUGIN_ABI 8
 
 #endif /* GGRS_AMD_GAME_HPP */
