@@ -29,5 +29,6 @@ from .p2p import P2PSession, PlayerType, synth_network  # noqa: F401
 from .spectator import SpectatorSession  # noqa: F401
 from .migrate import move_sessions  # noqa: F401
 from .delivery_ring import DeliveryRing  # noqa: F401
+from .wire import decode_packets, encode_packets  # noqa: F401
 
 __version__ = "0.1.0"

@@ -216,6 +216,10 @@ SIGNATURES = [
                                         _P, _P]),
     ("rb_encode_input_packets", _I32, [_I32, _P, _I32, _I32, _I32, _I32, _P, _I32, _I32, _P, _P, _P, ctypes.c_int64,
                                         _P, _P]),
+    ("rb_decode_input_packets_all", _I32, [_I32, _P, ctypes.c_uint32, _I32, _I32, _I32, _I32, _P, ctypes.c_int64, _P, _P,
+                                            _P, _I32, _I32, _P, _P]),
+    ("rb_encode_input_packets_all", _I32, [_I32, _P, ctypes.c_uint32, _I32, _I32, _I32, _P, _I32, _I32, _I32, _P, _P, _P,
+                                            ctypes.c_int64, _P, _P]),
 ]
 
 # the entry points that return a 64-bit size

@@ -11,6 +11,12 @@ newly arrived frames into their slots with torch on the device: no host loop
 over sessions, and ``scatter`` does not synchronise (``restart`` and
 ``move_columns``, called when matches begin or move, may: a boolean mask or a
 host index list goes through the host).
+
+Over a real link the frames arrive as packets: ``receive_packets`` decodes every
+endpoint's packet into its slots and advances the watermarks in one launch, and
+``send_packets`` encodes out of a ring that ``export_local_inputs`` or
+``export_confirmed_inputs`` filled (rb_decode_input_packets_all,
+rb_encode_input_packets_all).
 """
 from __future__ import annotations
 
@@ -28,15 +34,17 @@ class DeliveryRing:
             raise ValueError("ring_frames is a power of two of at least 128")
         self.ring_frames, self.num_players, self.num_sessions = R, int(num_players), int(num_sessions)
         self.inputs = torch.zeros((R, self.num_players, self.num_sessions), dtype=dtype or torch.uint8, device=device)
-        if self.inputs.element_size() not in (1, 4):
-            raise ValueError("inputs of 1 or 4 bytes")
+        # 2-byte inputs serve the packet codec (receive_packets / send_packets); the batches
+        # themselves take inputs of 1 or 4 bytes
+        if self.inputs.element_size() not in (1, 2, 4):
+            raise ValueError("inputs of 1, 2 or 4 bytes")
         self.upto = torch.full((self.num_players, self.num_sessions), L.RB_NULL_FRAME, dtype=torch.int32, device=device)
         self._cols = torch.arange(self.num_sessions, device=device)
 
     def _raw(self, x):
-        """4-byte inputs as int32 (torch indexes few unsigned types); the bits are what counts."""
+        """4- and 2-byte inputs as int32 / int16 (torch indexes few unsigned types); the bits are what counts."""
         import torch
-        return x.view(torch.int32) if x.element_size() == 4 else x
+        return x.view({4: torch.int32, 2: torch.int16}[x.element_size()]) if x.element_size() != 1 else x
 
     def scatter(self, handle: int, first, count, values) -> None:
         """The frames that arrived for `handle`: session s got frames first[s] .. first[s] +
@@ -57,6 +65,31 @@ class DeliveryRing:
         plane[slot, cols] = torch.where(k < count[None, :], self._raw(values), plane[slot, cols])
         last = torch.where(count > 0, first + count - 1, torch.full_like(first, L.RB_NULL_FRAME)).to(torch.int32)
         self.upto[int(handle)] = torch.maximum(self.upto[int(handle)], last)
+
+    def receive_packets(self, handle_mask: int, packets, lengths, start_frames, max_prediction: int, status=None):
+        """UdpProtocol::on_input for every endpoint of the handles in handle_mask, in one launch
+        (wire.decode_packets in ring mode): packets uint8 [P, S, stride], lengths and start_frames
+        int32 [P, S].  New frames go to their slots and ``upto`` advances; a packet with more than R
+        new frames is taken up to R of them (the sender, acked with ``upto``, sends the rest again).
+        The batch must have consumed every frame up to ``upto`` before the call.  Returns the status
+        tensor [P, S] (0 new inputs, 1 nothing new, -1 malformed, -2 a gap; rows outside the mask
+        are left alone).  Does not synchronise."""
+        from .wire import decode_packets
+        return decode_packets(self.inputs, self.upto, handle_mask, packets, lengths, start_frames, max_prediction,
+                              status=status, ring_frames=self.ring_frames)
+
+    def send_packets(self, handle_mask: int, newest, acked, first_frame: int, packets, lengths, start_frames) -> None:
+        """UdpProtocol::send_pending_output for every endpoint of the handles in handle_mask, in one
+        launch (wire.encode_packets in ring mode), with this ring holding the sender's inputs (the
+        tensor of export_local_inputs or export_confirmed_inputs): frames acked + 1 .. newest
+        (first_frame .. newest before any ack) against the input of frame acked.  newest and acked
+        int32 [P, S] (`sent` of export_local_inputs; the receiver's ``upto`` as it came back).
+        lengths: bytes, 0 nothing pending, -1 longer than the stride, -2 more than R frames from the
+        ack to newest (the reference input is gone; the reference disconnects such an endpoint).
+        Does not synchronise."""
+        from .wire import encode_packets
+        encode_packets(self.inputs, handle_mask, newest, acked, first_frame, packets, lengths, start_frames,
+                       ring_frames=self.ring_frames)
 
     def restart(self, sessions) -> None:
         """The sessions (a bool / index tensor or array) begin a new match: their watermarks are

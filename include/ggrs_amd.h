@@ -995,6 +995,69 @@ rb_status rb_encode_input_packets(int32_t device, void* stream, int32_t handle, 
                                   int32_t first_frame, const int32_t* acked, const int32_t* newest, uint8_t* packets,
                                   int64_t packet_stride, int32_t* lengths, int32_t* start_frames);
 
+/* ---- The codec for every endpoint of a batch in one launch, into and out of
+ * a linear tensor or a delivery ring.  Stateless like
+ * the pair above.  The endpoint of handle h, session s has its packet at
+ * packets + (h*S + s)*packet_stride and its length and start frame at
+ * lengths[h*S + s] and start_frames[h*S + s]: one tick of
+ * rb_p2p_run_ticks_packets' layout, so one packet tensor feeds either path.
+ * upto, status, acked and newest are int32 [num_players][S]; upto is a
+ * remote_upto row of rb_p2p_run_ticks (and the ack the receiver returns to
+ * the sender), newest the `sent` tensor of rb_p2p_export_local_inputs.
+ * handle_mask: the handles served.  Every row of a handle outside it is
+ * untouched, in every tensor.
+ * packet_stride is a multiple of 16 of at least 32 and packets is 16-byte
+ * aligned (the rule of rb_p2p_run_ticks_packets).
+ * ring_frames == 0: `inputs` is linear, [frames][num_players][S].
+ * ring_frames == R: `inputs` is a delivery ring [R][num_players][S], frame f
+ * in slot f & (R - 1); no frame is clamped.
+ * RB_INVALID_REQUEST, with nothing launched and no tensor touched: an empty
+ * mask or bits at or above num_players; num_players > 4; input_bytes not 1, 2
+ * or 4; a bad stride or alignment; ring_frames neither 0 nor a power of two of
+ * at least RB_INPUT_QUEUE_LENGTH; ring_frames != 0 with frames != ring_frames
+ * (the rule of rb_p2p_set_delivery_ring); in decode, 2*max_prediction >=
+ * ring_frames (a packet's reference input may be that old and must still be
+ * in the ring).
+ * Addresses stay inside the tensors for any lengths, start_frames, upto, acked
+ * and newest; results are defined for frames below 2^30.  Frames near
+ * INT32_MAX are out of range: nothing faults, the values are unspecified.
+ *
+ * Decode, linear: per endpoint bit for bit rb_decode_input_packets (status
+ * codes, the start - 1 >= frames refusal, no write at or above `frames`,
+ * validate-then-write).
+ * Decode, ring: the same checks in the same order (nothing / overlong / gap /
+ * stale reference / negative reference); the reference input is read from slot
+ * (start - 1) & (R - 1) before any store; the whole packet is validated, then
+ * written.  At most the first R frames above upto are written (no slot twice)
+ * and upto stops at the last frame written, so the sender, acked that far,
+ * sends the rest again (as rb_p2p_export_confirmed_inputs does in ring mode).
+ * The caller's contract: the consumer (rb_p2p_run_ticks, rb_spectator_run_ticks)
+ * has read every frame up to the upto handed in; then the frames written here
+ * overwrite only consumed slots, and after the call the contract of
+ * rb_p2p_set_delivery_ring holds for the new upto. */
+rb_status rb_decode_input_packets_all(int32_t device, void* stream, uint32_t handle_mask, int32_t num_players,
+                                      int32_t num_sessions, int32_t input_bytes, int32_t max_prediction,
+                                      const uint8_t* packets, int64_t packet_stride, const int32_t* lengths,
+                                      const int32_t* start_frames, void* inputs, int32_t frames, int32_t ring_frames,
+                                      int32_t* upto, int32_t* status);
+
+/* Encode, linear: lengths, start_frames and the packet's bytes are those of
+ * rb_encode_input_packets (bytes of the row past the packet's length are
+ * unspecified: the packet's first 32 bytes are stored as 16-byte words).
+ * Encode, ring: frames acked + 1 .. newest (first_frame .. newest before any
+ * ack) are read from their slots and the reference from slot acked & (R - 1).
+ * If frames (acked, or the start frame before any ack) .. newest do not fit R
+ * distinct slots the reference input has been overwritten: lengths = -2, no
+ * packet is written, start_frames is still set.  (The reference raises
+ * Event::Disconnected once more than 128 inputs are pending,
+ * protocol.rs:461-463; the caller decides what -2 means.)  0: nothing pending,
+ * -1: the packet does not fit packet_stride, as above. */
+rb_status rb_encode_input_packets_all(int32_t device, void* stream, uint32_t handle_mask, int32_t num_players,
+                                      int32_t num_sessions, int32_t input_bytes, const void* inputs, int32_t frames,
+                                      int32_t ring_frames, int32_t first_frame, const int32_t* acked,
+                                      const int32_t* newest, uint8_t* packets, int64_t packet_stride, int32_t* lengths,
+                                      int32_t* start_frames);
+
 #ifdef __cplusplus
 } /* extern "C" */
 #endif
