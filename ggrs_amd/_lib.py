@@ -44,6 +44,8 @@ RB_GAME_PLUGIN_BASE = 1000
 RB_P2P_REPORTS_PER_TAKE = 8
 RB_P2P_EVENTS_KEPT = 16
 RB_P2P_WAIT_EVENTS_KEPT = 8
+RB_P2P_NET_EVENTS_KEPT = 16
+RB_NET_INTERRUPTED, RB_NET_RESUMED, RB_NET_DISCONNECTED = 1, 2, 3
 RB_P2P_EXPORT_OK = 0
 RB_P2P_EXPORT_OVERRUN = 1
 SPECTATOR_BUFFER_SIZE = 60  # p2p_spectator_session.rs:16
@@ -188,6 +190,10 @@ SIGNATURES = [
     ("rb_p2p_run_ticks_paced", _I32, [_P, _I32, _P, ctypes.c_int64, _P, _P, _I32, _P]),
     ("rb_p2p_pace", _I32, [_P, _P]),
     ("rb_p2p_read_pacing", _I32, [_P, _P]),
+    ("rb_p2p_liveness_enable", _I32, [_P, _I32, _I32]),
+    ("rb_p2p_poll_liveness", _I32, [_P, ctypes.c_int64, _P, _P, _P]),
+    ("rb_p2p_read_network_events", _I32, [_P, _P, _P, _P, _P]),
+    ("rb_p2p_read_liveness", _I32, [_P, _P, _P]),
     ("rb_debug_time_sync_average", _I32, [_I32, _P, _P, _P, ctypes.c_int64]),
     ("rb_p2p_profile_enable", _I32, [_P, _I32]),
     ("rb_p2p_profile_take", _I32, [_P, ctypes.POINTER(ctypes.c_double), _PI32]),

@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "kernels.hpp"
+#include "liveness.hpp"
 #include "pacing.hpp"
 #define RB_RESTART_DEFINE  // restart_kernel and the move kernels live in this translation unit
 #include "migrate.hpp"
@@ -56,6 +57,9 @@ struct rb_p2p {
   int32_t ts_log_ticks = 0;
   PaceParams pace{};                  // rb_p2p_run_ticks_paced / rb_p2p_pace: the status view, parked ticks, the pacer's accumulator
   bool ticked = false;                // a tick has run (rb_p2p_time_sync_enable comes before the first)
+  LivenessParams lv{};                // rb_p2p_liveness_enable: stamps, flags, the event ring and the two delays (liveness.hpp)
+  bool lv_on = false;
+  int64_t lv_now = 0;                 // the newest now_ms a poll has passed
   int32_t ring_frames = 0;            // rb_p2p_set_delivery_ring: R, or 0 for linear by-frame tensors (host state only)
   DeviceOwner res;                    // every device buffer, pinned buffer and event of the batch
   bool prof = false;
@@ -114,13 +118,7 @@ __global__ void fan_sums_kernel(const unsigned long long* __restrict__ stats, in
 __global__ void p2p_disconnect_kernel(int32_t* qs, const uint8_t* mask, int32_t S, int32_t Spad, int32_t h) {
   const int s = blockIdx.x * blockDim.x + threadIdx.x;
   if (s >= S || (mask && !mask[s])) return;
-  const size_t sp = static_cast<size_t>(Spad);
-  auto row = [&](int field) -> int32_t& { return qs[(QS_PLAYER0 + field * 4 + h) * sp + s]; };
-  const int32_t cur = qs[QS_CUR * sp + s];
-  const uint32_t m = static_cast<uint32_t>(row(QF_MISC));
-  const int32_t last = (m & kQmEsc) ? row(QF_ABS0 + 1) : fd_dec(static_cast<uint32_t>(row(QF_LA_CONN)) >> 16, cur);
-  row(QF_MISC) = static_cast<int32_t>(m | kQmDisc);
-  if (cur > last) qs[QS_DISC_FRAME * sp + s] = last + 1;
+  p2p_disconnect_write(qs, static_cast<size_t>(Spad), s, h);
 }
 
 // UdpProtocol::on_checksum_report (protocol.rs:710-722) for the endpoint of
@@ -385,6 +383,14 @@ void pace_planes(rb_p2p* b, PlaneSet& ps) {
   ps.fill(b->pace.parked, 4, 1, 1, 0);
   ps.fill(b->pace.acc, 4, 1, 1, 0);
 }
+// every endpoint unstamped (its clock starts at its first poll), no flag, no event
+void liveness_planes(rb_p2p* b, PlaneSet& ps) {
+  if (!b->lv_on && !ps.make) return;
+  ps.fill(b->lv.stamp, 8, 4, 1, 0xff);  // kLvUnstamped
+  ps.fill(b->lv.flags, 1, 4, 1, 0);
+  ps.fill(b->lv.ev_n, 4, 1, 1, 0);
+  ps.carried(b->lv.ev, 4, static_cast<size_t>(LV_EV_ROWS) * kLvEvents, 1);  // the entries behind that count
+}
 // the groups create makes, the groups with templates first (their offsets are those of create)
 void create_planes(rb_p2p* b, PlaneSet& ps) {
   core_planes(b, ps);
@@ -418,6 +424,7 @@ void rb_p2p::planes(PlaneSet& ps) {
   export_planes(this, ps);
   time_sync_planes(this, ps);
   pace_planes(this, ps);
+  liveness_planes(this, ps);
 }
 
 extern "C" {
@@ -692,6 +699,7 @@ rb_status fan_after(rb_p2p* b, int32_t n) {
 
 namespace {
 constexpr const char* kTsOff = "time sync is off (rb_p2p_time_sync_enable)";
+constexpr const char* kLvOff = "liveness is off (rb_p2p_liveness_enable)";
 constexpr const char* kRingFrames =
     "the batch has a delivery ring (rb_p2p_set_delivery_ring): the by-frame tensor holds exactly ring_frames frames";
 // The tick log for a call of n ticks.  It grows to the largest call seen, and only once the stream
@@ -966,7 +974,7 @@ rb_status rb_p2p_restart_sessions(rb_p2p* b, const uint8_t* session_mask) {
 std::vector<uint32_t> rb_p2p::record_config() const {
   const rb_p2p* const b = this;
   const GameOps& o = *b->ops;
-  return {1u /* a P2P batch */,
+  std::vector<uint32_t> cfg{1u /* a P2P batch */,
           static_cast<uint32_t>(b->cfg.game),
           static_cast<uint32_t>(b->P),
           static_cast<uint32_t>(b->W),
@@ -985,6 +993,13 @@ std::vector<uint32_t> rb_p2p::record_config() const {
           b->ts_on ? static_cast<uint32_t>(b->ts.fps) : 0u,
           b->fanout ? (b->per_player ? 2u : 1u) : 0u,
           b->fanout ? static_cast<uint32_t>(b->cfg.fanout_candidates) : 0u};
+  // (appended only with liveness on: a batch without it keeps the record and fingerprint it had)
+  if (b->lv_on) {
+    cfg.push_back(1u);
+    cfg.push_back(static_cast<uint32_t>(b->lv.timeout_ms));
+    cfg.push_back(static_cast<uint32_t>(b->lv.notify_ms));
+  }
+  return cfg;
 }
 
 // the groups a later call would make, with create's fresh values: record_bytes depends on the
@@ -1357,6 +1372,83 @@ rb_status rb_p2p_read_desync_events(rb_p2p* b, uint32_t* counts, int32_t* frames
       if (handles) handles[o] = has ? hd[q * Sp + s] : -1;
       if (local_checksums) local_checksums[o] = has ? lo[q * Sp + s] : 0;
       if (remote_checksums) remote_checksums[o] = has ? ro[q * Sp + s] : 0;
+    }
+  }
+  return RB_OK;
+}
+
+// ---- endpoint liveness (liveness.hpp)
+rb_status rb_p2p_liveness_enable(rb_p2p* b, int32_t disconnect_timeout_ms, int32_t notify_start_ms) {
+  if (b->lv_on) return fail(b, RB_INVALID_REQUEST, "rb_p2p_liveness_enable: liveness is already on");
+  // disconnect_timeout - disconnect_notify_start is a Duration subtraction (protocol.rs:381): it panics below zero
+  if (notify_start_ms < 0 || disconnect_timeout_ms < notify_start_ms)
+    return fail(b, RB_INVALID_REQUEST, "rb_p2p_liveness_enable: needs 0 <= notify_start_ms <= disconnect_timeout_ms");
+  DeviceScope dev_scope(b->device);
+  if (const rb_status r = make_group(b, liveness_planes); r != RB_OK) return r;
+  b->lv.timeout_ms = disconnect_timeout_ms;
+  b->lv.notify_ms = notify_start_ms;
+  b->lv_on = true;
+  return RB_OK;
+}
+
+rb_status rb_p2p_poll_liveness(rb_p2p* b, int64_t now_ms, const uint8_t* received, const uint8_t* disconnect_requested,
+                               uint8_t* state_out) {
+  if (!b->lv_on) return fail(b, RB_INVALID_REQUEST, kLvOff);
+  if (!received) return fail(b, RB_INVALID_REQUEST, "rb_p2p_poll_liveness: missing received tensor");
+  if (now_ms < 0 || now_ms < b->lv_now)
+    return fail(b, RB_INVALID_REQUEST, "rb_p2p_poll_liveness: now_ms is non-negative and never runs backwards");
+  DeviceScope dev_scope(b->device);
+  auto k = b->P == 2 ? p2p_liveness_kernel<2> : b->P == 3 ? p2p_liveness_kernel<3> : p2p_liveness_kernel<4>;
+  hipLaunchKernelGGL(k, dim3((b->S + 255) / 256), dim3(256), 0, b->stream, b->lv, b->qs, b->status, received,
+                     disconnect_requested, state_out, now_ms, b->cfg.local_mask, b->S, b->Spad);
+  RB_TRY(b, hipGetLastError());
+  b->lv_now = now_ms;
+  b->mirror_stale = true;  // the timers disconnect players on the device
+  return RB_OK;
+}
+
+rb_status rb_p2p_read_network_events(rb_p2p* b, uint32_t* counts, int32_t* kinds, int32_t* handles, int32_t* values) {
+  if (!b->lv_on) return fail(b, RB_INVALID_REQUEST, kLvOff);
+  static_assert(kLvEvents == RB_P2P_NET_EVENTS_KEPT, "the event ring of liveness.hpp");
+  static_assert(kLvInterrupted == RB_NET_INTERRUPTED && kLvResumed == RB_NET_RESUMED && kLvDisconnected == RB_NET_DISCONNECTED,
+                "the event kinds of liveness_step.hpp");
+  DeviceScope dev_scope(b->device);
+  const size_t Sp = b->Spad, E = kLvEvents;
+  std::vector<uint32_t> n;
+  std::vector<int32_t> ev;
+  rb_status r = read_rows(b, b->lv.ev_n, 1, n);
+  if (r == RB_OK) r = read_rows(b, b->lv.ev, LV_EV_ROWS * E, ev);
+  if (r != RB_OK) return r;
+  for (int s = 0; s < b->S; ++s) {
+    const uint32_t cnt = n[s], kept = cnt < E ? cnt : static_cast<uint32_t>(E);
+    if (counts) counts[s] = cnt;
+    for (size_t e = 0; e < E; ++e) {  // oldest kept first
+      const bool has = e < kept;
+      const size_t q = (cnt - kept + e) % E, o = static_cast<size_t>(s) * E + e;
+      if (kinds) kinds[o] = has ? ev[(LV_EV_KIND * E + q) * Sp + s] : 0;
+      if (handles) handles[o] = has ? ev[(LV_EV_HANDLE * E + q) * Sp + s] : -1;
+      if (values) values[o] = has ? ev[(LV_EV_VALUE * E + q) * Sp + s] : 0;
+    }
+  }
+  return RB_OK;
+}
+
+rb_status rb_p2p_read_liveness(rb_p2p* b, int64_t* last_recv_ms, uint8_t* state) {
+  if (!b->lv_on) return fail(b, RB_INVALID_REQUEST, kLvOff);
+  DeviceScope dev_scope(b->device);
+  std::vector<int64_t> st;
+  std::vector<uint8_t> fl;
+  std::vector<int32_t> misc;
+  rb_status r = read_rows(b, b->lv.stamp, 4, st);
+  if (r == RB_OK) r = read_rows(b, b->lv.flags, 4, fl);
+  if (r == RB_OK) r = read_rows(b, b->qs + static_cast<size_t>(QS_PLAYER0 + QF_MISC * 4) * b->Spad, 4, misc);
+  if (r != RB_OK) return r;
+  for (int h = 0; h < b->P; ++h) {
+    const bool local = (b->cfg.local_mask >> h) & 1u;
+    for (int s = 0; s < b->S; ++s) {
+      const size_t o = static_cast<size_t>(h) * b->S + s, c = static_cast<size_t>(h) * b->Spad + s;
+      if (last_recv_ms) last_recv_ms[o] = local ? kLvUnstamped : st[c];
+      if (state) state[o] = local ? 0 : static_cast<uint8_t>(fl[c] | ((static_cast<uint32_t>(misc[c]) & kQmDisc) ? 4u : 0u));
     }
   }
   return RB_OK;

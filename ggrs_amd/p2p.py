@@ -199,7 +199,7 @@ class P2PSession(_Movable, _StreamOrdered):
         session is what a freshly created batch holds, its next tick is its frame 0 and its
         deliveries, packets and export rows count from 0 again.  The other sessions are untouched;
         counters() and totals() continue since create.  Read a session's desync events, wait
-        recommendations or parked ticks before restarting it."""
+        recommendations, network events or parked ticks before restarting it."""
         m = None
         if sessions is not None:
             m = np.ascontiguousarray(np.broadcast_to(np.asarray(sessions), (self.num_sessions,)), dtype=np.uint8)
@@ -490,6 +490,58 @@ class P2PSession(_Movable, _StreamOrdered):
         st = self._lib.rb_p2p_export_time_sync(self._h, ptrs[0], ptrs[1])
         self._post(cur, tuple(keep), outputs=True)
         self._check(st)
+
+    # -- endpoint liveness (protocol.rs:377-394, 555-562, 621-626; p2p_session.rs:818-847)
+    def enable_liveness(self, disconnect_timeout_ms: int = 2000, notify_start_ms: int = 500) -> None:
+        """SessionBuilder::with_disconnect_timeout / with_disconnect_notify_delay (builder.rs:175-184)
+        and the batch's receive timers on (rb_p2p_liveness_enable).  Once, before or after the
+        first tick; needs 0 <= notify_start_ms <= disconnect_timeout_ms."""
+        self._check(self._lib.rb_p2p_liveness_enable(self._h, int(disconnect_timeout_ms), int(notify_start_ms)))
+
+    def poll_liveness(self, now_ms: int, received, disconnect_requested=None, state_out=None) -> None:
+        """The timer half of poll_remote_clients for every session at the caller's clock `now_ms`
+        (rb_p2p_poll_liveness): one launch, stream ordered, no host copy.  uint8 CUDA tensors [P, S]:
+        received (a message of any kind came from that endpoint since the last poll),
+        disconnect_requested (None, or the flag of the peer's Input message) and state_out (None, or
+        written: bit 0 notify sent, bit 1 disconnect event sent, bit 2 player disconnected).  A silent
+        peer raises NetworkInterrupted, then Disconnected, and is disconnected as by
+        disconnect_player; between run_ticks calls."""
+        import torch
+        shape = (self.num_players, self.num_sessions)
+        ptrs, keep = [], []
+        for x in (received, disconnect_requested, state_out):
+            if x is None:
+                ptrs.append(None)
+                continue
+            assert x.is_cuda and x.is_contiguous() and x.dtype == torch.uint8 and tuple(x.shape) == shape
+            ptrs.append(ctypes.c_void_p(x.data_ptr()))
+            keep.append(x)
+        assert received is not None
+        cur = self._pre()
+        st = self._lib.rb_p2p_poll_liveness(self._h, int(now_ms), ptrs[0], ptrs[1], ptrs[2])
+        self._post(cur, tuple(keep), outputs=state_out is not None)
+        self._check(st)
+
+    def network_events(self):
+        """(counts [S], kinds [S, E], handles [S, E], values [S, E]): GGRSEvent::NetworkInterrupted
+        (RB_NET_INTERRUPTED, value = disconnect_timeout in ms), NetworkResumed and Disconnected per
+        session since enable_liveness or its restart, the newest E = RB_P2P_NET_EVENTS_KEPT in order
+        (kind 0, handle -1: none)."""
+        E = L.RB_P2P_NET_EVENTS_KEPT
+        n = np.empty(self.num_sessions, np.uint32)
+        kd, hd, vl = (np.empty((self.num_sessions, E), np.int32) for _ in range(3))
+        p = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+        self._check(self._lib.rb_p2p_read_network_events(self._h, p(n), p(kd), p(hd), p(vl)))
+        return n, kd, hd, vl
+
+    def read_liveness(self):
+        """(last_recv_ms int64 [P, S], state uint8 [P, S]): every endpoint's last receive time on the
+        caller's clock (-1: no poll yet, and local handles) and poll_liveness's state_out bits."""
+        st = np.empty((self.num_players, self.num_sessions), np.int64)
+        fl = np.empty((self.num_players, self.num_sessions), np.uint8)
+        self._check(self._lib.rb_p2p_read_liveness(self._h, st.ctypes.data_as(ctypes.c_void_p),
+                                                   fl.ctypes.data_as(ctypes.c_void_p)))
+        return st, fl
 
     def debug_time_sync_windows(self):
         """The TimeSync windows, int32 [2 (local, remote), 30, P, S] (tests)."""

@@ -793,6 +793,85 @@ rb_status rb_p2p_pace(rb_p2p* b, uint8_t* run_mask_dev);
  * the paced ticks, whatever made their masks).  Synchronises. */
 rb_status rb_p2p_read_pacing(rb_p2p* b, uint32_t* parked_ticks);
 
+/* ---- Endpoint liveness: deciding that a peer has gone
+ * silent.  UdpProtocol keeps last_recv_time and two flags per endpoint:
+ * handle_message stamps the time on every message of any kind and raises
+ * NetworkResumed if the notify had been sent (network/protocol.rs:555-562);
+ * on_input raises Disconnected when the peer's Input carries
+ * disconnect_requested (:621-626); poll raises NetworkInterrupted after
+ * disconnect_notify_start without a message and Disconnected after
+ * disconnect_timeout (:377-394).  P2PSession::handle_event forwards the first
+ * two and answers Disconnected with disconnect_player_at_frame(handle,
+ * local_connect_status[handle].last_frame) (sessions/p2p_session.rs:818-847).
+ * The sockets stay the caller's; the timers need only its clock and one
+ * "something arrived" byte per endpoint.  An optional group of a P2P batch:
+ * off unless enabled, and with it off nothing changes anywhere.
+ *
+ * rb_p2p_liveness_enable is SessionBuilder::with_disconnect_timeout /
+ * with_disconnect_notify_delay (builder.rs:175-184; the defaults are 2000 and
+ * 500 ms).  RB_INVALID_REQUEST with nothing changed: a second call; delays
+ * outside 0 <= notify_start_ms <= disconnect_timeout_ms (the Duration
+ * subtraction of protocol.rs:381 panics where the notify delay exceeds the
+ * timeout).  Before or after the first tick: no tick kernel reads its planes.
+ * Works with every configuration of rb_p2p_run_ticks, rb_p2p_run_ticks_paced
+ * (a parked session is polled like any other) and rb_p2p_run_ticks_packets.
+ * rb_p2p_restart_sessions resets the selected sessions' stamps, flags and
+ * event count; a move carries them, between batches with equal delays only
+ * (they enter the fingerprint when liveness is on; a batch without it keeps
+ * the record and fingerprint it had).  The stamps are the caller's clock: two
+ * batches that exchange records share one clock. */
+#define RB_P2P_NET_EVENTS_KEPT 16 /* newest network events kept per session */
+#define RB_NET_INTERRUPTED 1   /* value = disconnect_timeout_ms - notify_start_ms (protocol.rs:381-384) */
+#define RB_NET_RESUMED 2       /* protocol.rs:559-562 */
+#define RB_NET_DISCONNECTED 3  /* protocol.rs:388-394, 621-626 */
+rb_status rb_p2p_liveness_enable(rb_p2p* b, int32_t disconnect_timeout_ms, int32_t notify_start_ms);
+
+/* The timer half of one poll_remote_clients (p2p_session.rs:375-415) for every
+ * session: one launch, stream ordered, no synchronisation.  Called between
+ * tick calls, before the tick call whose watermarks deliver what this poll
+ * received.  now_ms: the caller's clock in milliseconds, >= 0 and never below
+ * the previous call's (else RB_INVALID_REQUEST, nothing launched).  Device
+ * uint8 [num_players][S] each, entries of local handles ignored / written 0:
+ *   received              non-zero: at least one message of any kind came from
+ *                         that endpoint since the previous poll
+ *   disconnect_requested  may be NULL; the flag of the peer's Input message
+ *   state_out             may be NULL; the flags after the call: bit 0
+ *                         disconnect_notify_sent, bit 1 disconnect_event_sent,
+ *                         bit 2 the player is disconnected
+ * A panicked session is skipped.  Otherwise every remote handle is taken in
+ * ascending order; a handle whose ConnectionStatus::disconnected is set still
+ * stamps but raises nothing (its endpoint no longer runs, protocol.rs:396-401).
+ * For the others, in this order:
+ *   1. an endpoint that has met no poll yet is stamped now_ms (the reference
+ *      stamps at construction, :260: a deviation of at most one poll);
+ *   2. received: the stamp becomes now_ms; bit 0 set: cleared, RB_NET_RESUMED;
+ *   3. disconnect_requested and bit 1 clear: bit 1 set, RB_NET_DISCONNECTED;
+ *   4. bit 0 clear and stamp + notify_start_ms < now_ms: bit 0 set,
+ *      RB_NET_INTERRUPTED with value disconnect_timeout_ms - notify_start_ms;
+ *   5. bit 1 clear and stamp + disconnect_timeout_ms < now_ms: bit 1 set,
+ *      RB_NET_DISCONNECTED;
+ *   6. a RB_NET_DISCONNECTED of this poll disconnects the player exactly as
+ *      rb_p2p_disconnect_player does (resimulation from last_frame + 1).
+ * Both comparisons are strict, in 64 bits.  A session's events of one poll are
+ * ordered by handle, then as above (the reference walks a HashMap of
+ * endpoints: it has no order across handles).  The next
+ * rb_p2p_disconnect_player reads the connect status back first, so "Player
+ * already disconnected." holds for a player the timers disconnected. */
+rb_status rb_p2p_poll_liveness(rb_p2p* b, int64_t now_ms, const uint8_t* received,
+                               const uint8_t* disconnect_requested, uint8_t* state_out);
+
+/* Network events per session: counts[S] since enable or restart, and the newest
+ * RB_P2P_NET_EVENTS_KEPT in order as kinds (RB_NET_*) / remote handles / values,
+ * each [S][RB_P2P_NET_EVENTS_KEPT] (kind 0, handle -1, value 0: none).  Any
+ * pointer may be NULL.  Synchronises. */
+rb_status rb_p2p_read_network_events(rb_p2p* b, uint32_t* counts, int32_t* kinds, int32_t* handles, int32_t* values);
+
+/* last_recv_time in the caller's milliseconds (-1: no poll yet, and local
+ * handles) as last_recv_ms int64 [num_players][S], and rb_p2p_poll_liveness's
+ * state_out bits as state uint8 [num_players][S].  Either may be NULL.
+ * Synchronises. */
+rb_status rb_p2p_read_liveness(rb_p2p* b, int64_t* last_recv_ms, uint8_t* state);
+
 /* TimeSync::average_frame_advantage (time_sync.rs:30-39) from the windows' sums
  * for n host (local_sum, remote_sum) pairs: device < 0 on the host, else by a
  * kernel on that device (the same function, time_sync.hpp). */
