@@ -46,6 +46,9 @@ RB_P2P_EVENTS_KEPT = 16
 RB_P2P_WAIT_EVENTS_KEPT = 8
 RB_P2P_NET_EVENTS_KEPT = 16
 RB_NET_INTERRUPTED, RB_NET_RESUMED, RB_NET_DISCONNECTED = 1, 2, 3
+RB_DG_MALFORMED, RB_DG_MAGIC_MISMATCH, RB_DG_SYNC_SEEN, RB_DG_BAD_PONG, RB_DG_REPORTS_DROPPED = 1, 2, 4, 8, 16
+RB_DG_NO_ROOM, RB_DG_ADVANTAGE_RANGE = 32, 64
+RB_DG_MAX_SLOTS = 8
 RB_P2P_EXPORT_OK = 0
 RB_P2P_EXPORT_OVERRUN = 1
 SPECTATOR_BUFFER_SIZE = 60  # p2p_spectator_session.rs:16
@@ -109,6 +112,63 @@ class RbChecksumReport(ctypes.Structure):
         ("checksum_hi", ctypes.c_uint64),
         ("frame", ctypes.c_int32),
         ("mismatch_frame", ctypes.c_int32),
+    ]
+
+
+class RbDatagramParse(ctypes.Structure):
+    _fields_ = [
+        ("datagrams", ctypes.c_void_p),
+        ("stride", ctypes.c_int64),
+        ("slots", ctypes.c_int32),
+        ("reserved", ctypes.c_int32),
+        ("dg_lengths", ctypes.c_void_p),
+        ("remote_magic", ctypes.c_void_p),
+        ("now_ms", ctypes.c_int64),
+        ("received", ctypes.c_void_p),
+        ("disconnect_requested", ctypes.c_void_p),
+        ("acked", ctypes.c_void_p),
+        ("peer_last_frames", ctypes.c_void_p),
+        ("peer_disconnected", ctypes.c_void_p),
+        ("packets", ctypes.c_void_p),
+        ("packet_stride", ctypes.c_int64),
+        ("lengths", ctypes.c_void_p),
+        ("start_frames", ctypes.c_void_p),
+        ("frame_advantage", ctypes.c_void_p),
+        ("reply_owed", ctypes.c_void_p),
+        ("reply_ping", ctypes.c_void_p),
+        ("rtt_ms", ctypes.c_void_p),
+        ("reports", ctypes.c_void_p),
+        ("report_counts", ctypes.c_void_p),
+        ("status", ctypes.c_void_p),
+    ]
+
+
+class RbDatagramBuild(ctypes.Structure):
+    _fields_ = [
+        ("local_magic", ctypes.c_void_p),
+        ("now_ms", ctypes.c_int64),
+        ("packets", ctypes.c_void_p),
+        ("packet_stride", ctypes.c_int64),
+        ("lengths", ctypes.c_void_p),
+        ("start_frames", ctypes.c_void_p),
+        ("ack_frame", ctypes.c_void_p),
+        ("disconnect_requested", ctypes.c_void_p),
+        ("status_last_frames", ctypes.c_void_p),
+        ("status_disconnected", ctypes.c_void_p),
+        ("ack_owed", ctypes.c_void_p),
+        ("reply_owed", ctypes.c_void_p),
+        ("reply_ping", ctypes.c_void_p),
+        ("report_due", ctypes.c_void_p),
+        ("frame_advantage", ctypes.c_void_p),
+        ("reports", ctypes.c_void_p),
+        ("keepalive_due", ctypes.c_void_p),
+        ("out_datagrams", ctypes.c_void_p),
+        ("stride", ctypes.c_int64),
+        ("slots", ctypes.c_int32),
+        ("reserved", ctypes.c_int32),
+        ("out_lengths", ctypes.c_void_p),
+        ("out_counts", ctypes.c_void_p),
+        ("status", ctypes.c_void_p),
     ]
 
 
@@ -226,6 +286,8 @@ SIGNATURES = [
                                             _P, _I32, _I32, _P, _P]),
     ("rb_encode_input_packets_all", _I32, [_I32, _P, ctypes.c_uint32, _I32, _I32, _I32, _P, _I32, _I32, _I32, _P, _P, _P,
                                             ctypes.c_int64, _P, _P]),
+    ("rb_parse_datagrams_all", _I32, [_I32, _P, ctypes.c_uint32, _I32, _I32, ctypes.POINTER(RbDatagramParse)]),
+    ("rb_build_datagrams_all", _I32, [_I32, _P, ctypes.c_uint32, _I32, _I32, ctypes.POINTER(RbDatagramBuild)]),
 ]
 
 # the entry points that return a 64-bit size

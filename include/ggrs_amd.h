@@ -1137,6 +1137,185 @@ rb_status rb_encode_input_packets_all(int32_t device, void* stream, uint32_t han
                                       const int32_t* newest, uint8_t* packets, int64_t packet_stride, int32_t* lengths,
                                       int32_t* start_frames);
 
+/* ---- GGRS's wire messages for every endpoint of a batch in one launch
+ * (DESIGN.md section 19): the datagrams the reference puts on its socket,
+ * Message { header: { magic }, body: MessageBody } under bincode::serialize
+ * (network/messages.rs, network/udp_socket.rs:31-45).  Stateless like the codec
+ * above and laid out like it: the endpoint of handle h, session s is row
+ * h*S + s of every [P][S] tensor, handle_mask selects the handles served, and
+ * no row of a handle outside it is touched, in any tensor.
+ *
+ * bincode 1.3 as the free functions serialize / deserialize use it: fixed-width
+ * little-endian integers, an enum variant is a u32, a Vec length a u64, a bool
+ * one byte that must be 0 or 1, an i8 one byte, a u128 16 bytes.  A datagram is
+ * magic u16, variant u32, then
+ *   0 SyncRequest     u32
+ *   1 SyncReply       u32
+ *   2 Input           u64 n, n x (bool disconnected, i32 last_frame),
+ *                     bool disconnect_requested, i32 start_frame, i32 ack_frame,
+ *                     u64 len, len bytes
+ *   3 InputAck        i32 ack_frame
+ *   4 QualityReport   i8 frame_advantage, u128 ping
+ *   5 QualityReply    u128 pong
+ *   6 ChecksumReport  u128 checksum, i32 frame
+ *   7 KeepAlive
+ * Trailing bytes are accepted; a short buffer, a variant above 7, a bool above 1
+ * or a length that runs past the buffer is malformed, and the reference's socket
+ * drops such a datagram before handle_message sees it (udp_socket.rs:42).
+ *
+ * Status bits, int32 [P][S], written by every call for every endpoint served: */
+#define RB_DG_MALFORMED 1         /* parse: a datagram bincode refuses, or an Input with n != num_players */
+#define RB_DG_MAGIC_MISMATCH 2    /* parse: dropped by protocol.rs:551 */
+#define RB_DG_SYNC_SEEN 4         /* parse: a SyncRequest / SyncReply came; it stamps `received` and is not answered */
+#define RB_DG_BAD_PONG 8          /* parse: a QualityReply from the future, or a round trip beyond int32 */
+#define RB_DG_REPORTS_DROPPED 16  /* parse: more than RB_P2P_REPORTS_PER_TAKE reports were pending */
+#define RB_DG_NO_ROOM 32          /* build: a message did not fit the slots or the stride and was left out */
+#define RB_DG_ADVANTAGE_RANGE 64  /* build: frame_advantage outside i8; no QualityReport (the reference panics, protocol.rs:519-520) */
+#define RB_DG_MAX_SLOTS 8
+
+/* UdpProtocol::handle_message (protocol.rs:544-575) with on_input's head
+ * (:616-637), on_input_ack (:692-694), on_quality_report / on_quality_reply
+ * (:697-708) and the collecting half of on_checksum_report (:710-722) for every
+ * endpoint: the datagrams the caller's sockets collected since the last call, in
+ * up to RB_DG_MAX_SLOTS slots per endpoint, handled in slot order.  Every
+ * pointer is device memory and none may be NULL.
+ *   datagrams        uint8 [slots][P*S][stride], 16-byte aligned; stride a
+ *                    multiple of 16 of at least 64
+ *   dg_lengths       int32 [slots][P][S]; 0 or negative: an empty slot.  No byte
+ *                    at or above min(length, stride) decides anything
+ *   remote_magic     uint16 [P][S]; 0 accepts any magic (:551)
+ *   now_ms           the caller's epoch clock, >= 0 (millis_since_epoch)
+ * For each datagram accepted (well formed, magic right):
+ *   received         uint8 [P][S] = 1, else 0: rb_p2p_poll_liveness's tensor
+ *   Input            acked (in/out int32 [P][S]) = max(acked, ack_frame);
+ *                    disconnect_requested (uint8 [P][S], 0 otherwise) |= flag;
+ *                    with the flag clear the status vector is merged into
+ *                    peer_last_frames int32 [P endpoints][P players][S] (max,
+ *                    from RB_NULL_FRAME) and peer_disconnected uint8, same shape
+ *                    (OR, from 0), over this call's messages: the merge is
+ *                    monotone, so rb_p2p_receive_peer_connect_status(h, row h)
+ *                    equals applying each message in turn (:627-636).  An Input
+ *                    whose n is not num_players is malformed (the reference
+ *                    indexes past a short vector and panics).  The payload of
+ *                    the last Input in slot order goes to packets / lengths /
+ *                    start_frames in rb_decode_input_packets_all's layout
+ *                    (lengths 0: none; bytes of the row past the payload are
+ *                    unspecified); earlier Inputs of the call count as lost
+ *                    datagrams for their payload only, and the sender repeats
+ *                    what was not acknowledged.  A payload longer than
+ *                    packet_stride leaves its true length and its first
+ *                    packet_stride bytes: the decoder refuses that length.
+ *   InputAck         acked = max(acked, ack_frame)
+ *   QualityReport    frame_advantage (in/out int32 [P][S]) takes the value,
+ *                    reply_owed uint8 [P][S] = 1 (else 0) and reply_ping
+ *                    uint64 [2 lo, hi][P][S] the u128 to echo (else 0); the last
+ *                    report wins
+ *   QualityReply     rtt_ms (in/out int32 [P][S]) = now_ms - pong; a pong above
+ *                    now_ms (the reference asserts, :706) or a difference beyond
+ *                    int32 leaves rtt_ms and sets RB_DG_BAD_PONG
+ *   ChecksumReport   appended to reports [P][RB_P2P_REPORTS_PER_TAKE][S]
+ *                    rb_checksum_report behind the report_counts (in/out int32
+ *                    [P][S]) entries already there; handle h's slice is what
+ *                    rb_p2p_receive_checksum_reports(h, slice,
+ *                    RB_P2P_REPORTS_PER_TAKE) takes, after which the caller
+ *                    zeroes report_counts[h].  Entries at and above the count
+ *                    are written RB_NULL_FRAME (mismatch_frame RB_NULL_FRAME,
+ *                    checksum 0) by every call.  Beyond the capacity the oldest
+ *                    leave and RB_DG_REPORTS_DROPPED is set.
+ *   SyncRequest / SyncReply   RB_DG_SYNC_SEEN, nothing else
+ * RB_INVALID_REQUEST, with nothing launched and no tensor touched: an empty mask
+ * or bits at or above num_players; num_players > 4; slots outside
+ * 1..RB_DG_MAX_SLOTS; a stride or packet_stride that breaks the rules above /
+ * of rb_decode_input_packets_all, or a misaligned datagrams / packets pointer;
+ * now_ms < 0; a NULL pointer. */
+typedef struct rb_datagram_parse {
+  const uint8_t* datagrams;
+  int64_t stride;
+  int32_t slots;
+  int32_t reserved;
+  const int32_t* dg_lengths;
+  const uint16_t* remote_magic;
+  int64_t now_ms;
+  uint8_t* received;
+  uint8_t* disconnect_requested;
+  int32_t* acked;
+  int32_t* peer_last_frames;
+  uint8_t* peer_disconnected;
+  uint8_t* packets;
+  int64_t packet_stride;
+  int32_t* lengths;
+  int32_t* start_frames;
+  int32_t* frame_advantage;
+  uint8_t* reply_owed;
+  uint64_t* reply_ping;
+  int32_t* rtt_ms;
+  rb_checksum_report* reports;
+  int32_t* report_counts;
+  int32_t* status;
+} rb_datagram_parse;
+rb_status rb_parse_datagrams_all(int32_t device, void* stream, uint32_t handle_mask, int32_t num_players,
+                                 int32_t num_sessions, const rb_datagram_parse* io);
+
+/* The messages every endpoint owes this poll, as queue_message's callers build
+ * them (protocol.rs:468-525, 736-742), packed densely per endpoint in this
+ * order into out_datagrams uint8 [slots][P*S][stride] (16-byte aligned, stride
+ * as above), their lengths in out_lengths int32 [slots][P][S] (0: an empty
+ * slot; bytes of a row past the length are unspecified) and their number in
+ * out_counts int32 [P][S]:
+ *   1. Input, where lengths > 0: the packet rb_encode_input_packets_all wrote
+ *      (packets / packet_stride / lengths / start_frames), ack_frame (int32
+ *      [P][S]: the `upto` row, last_recv_frame), disconnect_requested (uint8
+ *      [P][S]) and the sender's connect status, status_last_frames int32 /
+ *      status_disconnected uint8 [P players][S] (:468-492).  A length above
+ *      packet_stride is no packet: RB_DG_MALFORMED, no Input.
+ *   2. InputAck{ack_frame}, where ack_owed uint8 [P][S] is set (:495-501)
+ *   3. QualityReply, where reply_owed is set, echoing reply_ping (the tensors
+ *      rb_parse_datagrams_all wrote)
+ *   4. QualityReport, where report_due uint8 [P][S] is set (:516-525):
+ *      frame_advantage int32 [P][S] is the local_adv row of
+ *      rb_p2p_export_time_sync (outside i8: RB_DG_ADVANTAGE_RANGE and no
+ *      message); ping = now_ms
+ *   5. a ChecksumReport for every entry of reports [RB_P2P_REPORTS_PER_TAKE][S]
+ *      (rb_p2p_take_checksum_reports' tensor) whose frame is not RB_NULL_FRAME,
+ *      the same for every endpoint of a session (:736-742)
+ *   6. KeepAlive, where keepalive_due uint8 [P][S] is set and nothing else was
+ *      written for the endpoint
+ * A message that does not fit the slots left or the stride is left out and sets
+ * RB_DG_NO_ROOM; the ones after it are still tried.  local_magic is uint16
+ * [P][S].  Which bytes are due is the caller's decision (the 200 ms send timers
+ * are its own).  NULL means "none due" for packets (with lengths and
+ * start_frames), disconnect_requested, ack_owed, reply_owed (with reply_ping),
+ * report_due (with frame_advantage), reports and keepalive_due; the other
+ * pointers may not be NULL.  RB_INVALID_REQUEST as for rb_parse_datagrams_all. */
+typedef struct rb_datagram_build {
+  const uint16_t* local_magic;
+  int64_t now_ms;
+  const uint8_t* packets;
+  int64_t packet_stride;
+  const int32_t* lengths;
+  const int32_t* start_frames;
+  const int32_t* ack_frame;
+  const uint8_t* disconnect_requested;
+  const int32_t* status_last_frames;
+  const uint8_t* status_disconnected;
+  const uint8_t* ack_owed;
+  const uint8_t* reply_owed;
+  const uint64_t* reply_ping;
+  const uint8_t* report_due;
+  const int32_t* frame_advantage;
+  const rb_checksum_report* reports;
+  const uint8_t* keepalive_due;
+  uint8_t* out_datagrams;
+  int64_t stride;
+  int32_t slots;
+  int32_t reserved;
+  int32_t* out_lengths;
+  int32_t* out_counts;
+  int32_t* status;
+} rb_datagram_build;
+rb_status rb_build_datagrams_all(int32_t device, void* stream, uint32_t handle_mask, int32_t num_players,
+                                 int32_t num_sessions, const rb_datagram_build* io);
+
 #ifdef __cplusplus
 } /* extern "C" */
 #endif

@@ -5,7 +5,8 @@
 
 A p2p_kernel instantiation is printed with its variant's flags by name (p2p_variant.hpp P2PFlag),
 p2p_kernel<ExGame<2, true>, LdsC|Async|Log>.  With --against REPORT (a report of another commit,
-made the same way) every p2p_kernel line is followed by how it compares with the instantiation of
+made the same way) every kernel line of a translation unit the other report lists is followed by
+how it compares with that report; a p2p_kernel line compares with the instantiation of
 the same flags there; a report from when the flags were ten positional bool template arguments
 (missing trailing ones false) is read as the same names.  Instantiations only the other report has
 are listed at the end.
@@ -59,9 +60,11 @@ def load_report(path):
 def main():
     base = load_report(AGAINST) if AGAINST else None
     same = changed = added = 0
+    other = [0, 0, 0]  # the kernels that are no p2p_kernel, where the other report lists their translation unit: same, changed, new
     print(f"# {' '.join(FLAGS)} (+ -mllvm -amdgpu-sched-strategy=max-ilp for ops_exgame_p*, as the Makefile)")
     print(f"# {'VGPR':>4s} {'AGPR':>4s} {'SGPR':>4s} {'SGPR spill':>10s} {'VGPR spill':>10s} {'scratch B/lane':>14s} "
           f"{'waves/SIMD':>10s} {'LDS B':>6s}  kernel")
+    listed = []
     for tu in TUS:
         extra = ["-mllvm", "-amdgpu-sched-strategy=max-ilp"] if tu.startswith("ops_exgame_p") else []
         with tempfile.TemporaryDirectory() as td:
@@ -103,6 +106,12 @@ def main():
                 else:
                     changed += 1
                     note = f"   [CHANGED, parent: {' '.join(map(str, old))}]"
+            elif base is not None and any(k[0] == tu for k in list(base) + listed):
+                old = base.pop((tu, n), None)
+                listed.append((tu, n))
+                other[0 if old == vals else 2 if old is None else 1] += 1
+                note = ("   [= parent]" if old == vals else "   [new]" if old is None
+                        else f"   [CHANGED, parent: {' '.join(map(str, old))}]")
             print(f"  {vals[0]:4d} {vals[1]:4d} {vals[2]:4d} {vals[3]:10d} {vals[4]:10d} "
                   f"{vals[5]:14d} {vals[6]:10d} {vals[7]:6d}  {n}{note}")
     if base is not None:
@@ -111,6 +120,11 @@ def main():
             print(f"# only in {os.path.basename(AGAINST)}: {tu} {n}")
         print(f"# p2p_kernel instantiations against {os.path.basename(AGAINST)}: {same} unchanged, {changed} changed, "
               f"{added} new" + (f", {len(gone)} GONE" if gone else ""))
+        lost = sorted(k for k in base if k[0] in TUS and not k[1].startswith("p2p_kernel<"))
+        for tu, n in lost:
+            print(f"# only in {os.path.basename(AGAINST)}: {tu} {n}")
+        print(f"# other kernels (codec, liveness, engines) against {os.path.basename(AGAINST)}: {other[0]} unchanged, "
+              f"{other[1]} changed, {other[2]} new" + (f", {len(lost)} GONE" if lost else ""))
 
 
 if __name__ == "__main__":
