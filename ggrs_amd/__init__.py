@@ -31,5 +31,6 @@ from .migrate import move_sessions  # noqa: F401
 from .delivery_ring import DeliveryRing  # noqa: F401
 from .wire import decode_packets, encode_packets  # noqa: F401
 from .datagram import ParsedDatagrams, build_datagrams, parse_datagrams  # noqa: F401
+from .protocol import EndpointProtocol  # noqa: F401
 
 __version__ = "0.1.0"

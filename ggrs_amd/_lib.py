@@ -49,6 +49,9 @@ RB_NET_INTERRUPTED, RB_NET_RESUMED, RB_NET_DISCONNECTED = 1, 2, 3
 RB_DG_MALFORMED, RB_DG_MAGIC_MISMATCH, RB_DG_SYNC_SEEN, RB_DG_BAD_PONG, RB_DG_REPORTS_DROPPED = 1, 2, 4, 8, 16
 RB_DG_NO_ROOM, RB_DG_ADVANTAGE_RANGE = 32, 64
 RB_DG_MAX_SLOTS = 8
+RB_EP_INITIALIZING, RB_EP_SYNCHRONIZING, RB_EP_RUNNING, RB_EP_DISCONNECTED, RB_EP_SHUTDOWN = 0, 1, 2, 3, 4
+RB_EP_EVENT_SYNCHRONIZING, RB_EP_EVENT_SYNCHRONIZED = 1, 2
+RB_EP_STAMPS = 5
 RB_P2P_EXPORT_OK = 0
 RB_P2P_EXPORT_OVERRUN = 1
 SPECTATOR_BUFFER_SIZE = 60  # p2p_spectator_session.rs:16
@@ -172,6 +175,51 @@ class RbDatagramBuild(ctypes.Structure):
     ]
 
 
+class RbEndpointProtocol(ctypes.Structure):
+    _fields_ = [
+        ("ep_state", ctypes.c_void_p),
+        ("sync_remaining", ctypes.c_void_p),
+        ("sync_nonces", ctypes.c_void_p),
+        ("sync_valid", ctypes.c_void_p),
+        ("sync_next", ctypes.c_void_p),
+        ("stamps", ctypes.c_void_p),
+        ("packets_sent", ctypes.c_void_p),
+        ("last_newest", ctypes.c_void_p),
+        ("remote_magic", ctypes.c_void_p),
+        ("now_ms", ctypes.c_int64),
+        ("local_magic", ctypes.c_void_p),
+        ("start", ctypes.c_void_p),
+        ("datagrams", ctypes.c_void_p),
+        ("stride", ctypes.c_int64),
+        ("slots", ctypes.c_int32),
+        ("sync_slots", ctypes.c_int32),
+        ("dg_lengths", ctypes.c_void_p),
+        ("nonces", ctypes.c_void_p),
+        ("disconnected", ctypes.c_void_p),
+        ("ack_owed", ctypes.c_void_p),
+        ("reply_owed", ctypes.c_void_p),
+        ("received", ctypes.c_void_p),
+        ("newest", ctypes.c_void_p),
+        ("acked", ctypes.c_void_p),
+        ("lengths", ctypes.c_void_p),
+        ("reports", ctypes.c_void_p),
+        ("input_lengths", ctypes.c_void_p),
+        ("ack_due", ctypes.c_void_p),
+        ("reply_due", ctypes.c_void_p),
+        ("report_due", ctypes.c_void_p),
+        ("keepalive_due", ctypes.c_void_p),
+        ("sync_datagrams", ctypes.c_void_p),
+        ("sync_lengths", ctypes.c_void_p),
+        ("sync_counts", ctypes.c_void_p),
+        ("events", ctypes.c_void_p),
+        ("sync_count", ctypes.c_void_p),
+        ("liveness_received", ctypes.c_void_p),
+        ("send_queue_len", ctypes.c_void_p),
+        ("session_running", ctypes.c_void_p),
+        ("status", ctypes.c_void_p),
+    ]
+
+
 # Every symbol declared in include/ggrs_amd.h: (name, restype, argtypes).
 _P = ctypes.c_void_p
 _I32 = ctypes.c_int32
@@ -288,6 +336,7 @@ SIGNATURES = [
                                             ctypes.c_int64, _P, _P]),
     ("rb_parse_datagrams_all", _I32, [_I32, _P, ctypes.c_uint32, _I32, _I32, ctypes.POINTER(RbDatagramParse)]),
     ("rb_build_datagrams_all", _I32, [_I32, _P, ctypes.c_uint32, _I32, _I32, ctypes.POINTER(RbDatagramBuild)]),
+    ("rb_endpoint_protocol_poll_all", _I32, [_I32, _P, ctypes.c_uint32, _I32, _I32, ctypes.POINTER(RbEndpointProtocol)]),
 ]
 
 # the entry points that return a 64-bit size

@@ -1166,7 +1166,7 @@ rb_status rb_encode_input_packets_all(int32_t device, void* stream, uint32_t han
  * Status bits, int32 [P][S], written by every call for every endpoint served: */
 #define RB_DG_MALFORMED 1         /* parse: a datagram bincode refuses, or an Input with n != num_players */
 #define RB_DG_MAGIC_MISMATCH 2    /* parse: dropped by protocol.rs:551 */
-#define RB_DG_SYNC_SEEN 4         /* parse: a SyncRequest / SyncReply came; it stamps `received` and is not answered */
+#define RB_DG_SYNC_SEEN 4         /* parse: a SyncRequest / SyncReply came; it stamps `received`; rb_endpoint_protocol_poll_all answers it */
 #define RB_DG_BAD_PONG 8          /* parse: a QualityReply from the future, or a round trip beyond int32 */
 #define RB_DG_REPORTS_DROPPED 16  /* parse: more than RB_P2P_REPORTS_PER_TAKE reports were pending */
 #define RB_DG_NO_ROOM 32          /* build: a message did not fit the slots or the stride and was left out */
@@ -1282,8 +1282,10 @@ rb_status rb_parse_datagrams_all(int32_t device, void* stream, uint32_t handle_m
  *      written for the endpoint
  * A message that does not fit the slots left or the stride is left out and sets
  * RB_DG_NO_ROOM; the ones after it are still tried.  local_magic is uint16
- * [P][S].  Which bytes are due is the caller's decision (the 200 ms send timers
- * are its own).  NULL means "none due" for packets (with lengths and
+ * [P][S].  Which bytes are due is decided outside this call: by
+ * rb_endpoint_protocol_poll_all, below (the 200 ms send timers), whose outputs
+ * are this call's lengths, ack_owed, reply_owed, report_due and keepalive_due,
+ * or by the caller's own timers.  NULL means "none due" for packets (with lengths and
  * start_frames), disconnect_requested, ack_owed, reply_owed (with reply_ping),
  * report_due (with frame_advantage), reports and keepalive_due; the other
  * pointers may not be NULL.  RB_INVALID_REQUEST as for rb_parse_datagrams_all. */
@@ -1315,6 +1317,202 @@ typedef struct rb_datagram_build {
 } rb_datagram_build;
 rb_status rb_build_datagrams_all(int32_t device, void* stream, uint32_t handle_mask, int32_t num_players,
                                  int32_t num_sessions, const rb_datagram_build* io);
+
+/* ---- UdpProtocol's handshake, state machine and send timers for every endpoint
+ * of a batch in one launch: the part of
+ * network/protocol.rs that decides which message is due and when.  Stateless in
+ * the library like the two calls above and laid out like them: the endpoint of
+ * handle h, session s is row h*S + s of every [P][S] tensor, handle_mask selects
+ * the handles served, and no row of a handle outside it is touched, in any
+ * tensor.  The endpoint's state lives in the caller's tensors; a fresh endpoint
+ * is all zero bytes in every one of them, so restarting a session's endpoints
+ * means zeroing their columns.  ProtocolState (protocol.rs:119-125): */
+#define RB_EP_INITIALIZING 0
+#define RB_EP_SYNCHRONIZING 1
+#define RB_EP_RUNNING 2
+#define RB_EP_DISCONNECTED 3
+#define RB_EP_SHUTDOWN 4 /* and any byte above it: an unknown state is never run and never written */
+#define RB_EP_EVENT_SYNCHRONIZING 1 /* events bit 0: Event::Synchronizing{total 5, count sync_count} (:599-603) */
+#define RB_EP_EVENT_SYNCHRONIZED 2  /* events bit 1: Event::Synchronized (:610) */
+#define RB_EP_STAMPS 5 /* last_send, last_input_recv, last_quality_report, shutdown_at, stats_start */
+
+/* State, in/out, device memory, none NULL:
+ *   ep_state        uint8 [P][S]     RB_EP_* (UdpProtocol::state)
+ *   sync_remaining  int32 [P][S]     sync_remaining_roundtrips (:138)
+ *   sync_nonces     uint32 [8][P][S] sync_random_requests (:139), the newest 8
+ *                   outstanding nonces: the reference's HashSet grows without
+ *                   bound; here a reply to a request more than 8 requests old
+ *                   is ignored and the handshake goes on with the newer ones.
+ *                   Inserting a value that is already valid adds nothing, as a
+ *                   set does (the request is still sent, :507-514)
+ *   sync_valid      uint8 [P][S]     bit i: entry i of sync_nonces is outstanding
+ *   sync_next       uint8 [P][S]     the entry the next insert writes (read & 7)
+ *   stamps          int64 [RB_EP_STAMPS][P][S], the caller's milliseconds:
+ *                   last_send_time (:173), running_last_input_recv (:141),
+ *                   running_last_quality_report (:140), shutdown_timeout (:148),
+ *                   stats_start_time (:169)
+ *   packets_sent    int64 [P][S]     messages declared due so far (:170, :532)
+ *   last_newest     int32 [P][S]     1 + the newest local frame an Input was
+ *                   already declared due for (0: none, so that a zeroed row is
+ *                   an endpoint that has sent nothing)
+ *   remote_magic    uint16 [P][S]    the tensor rb_parse_datagrams_all takes;
+ *                   written here when the handshake ends (:612)
+ * Inputs; "optional" may be NULL, meaning none or zero:
+ *   now_ms          the caller's clock, >= 0
+ *   local_magic     uint16 [P][S]    UdpProtocol::magic (:198-201)
+ *   start           uint8 [P][S], optional: synchronize() (:335-341)
+ *   datagrams, stride, slots, dg_lengths: the tensors handed to
+ *                   rb_parse_datagrams_all.  Only variants 0 and 1 are read.
+ *                   stride a multiple of 16 of at least 16, the tensor 16-byte
+ *                   aligned
+ *   nonces          uint32 [slots][P][S]: rand::random::<u32>() is the caller's
+ *                   (:508).  The j-th SyncRequest an endpoint sends in this call
+ *                   uses nonces[j]; a request beyond the slots-th is not sent
+ *                   (RB_DG_NO_ROOM)
+ *   disconnected    uint8 [P][S], optional: bit 2 of rb_p2p_poll_liveness's
+ *                   state_out, or any non-zero byte: disconnect() (:325-333)
+ *   ack_owed        uint8 [P][S], optional: set where this poll's decode
+ *                   accepted an Input (the byte rb_build_datagrams_all takes)
+ *   reply_owed, received  rb_parse_datagrams_all's tensors, optional
+ *   newest          int32 [P][S]: the sent tensor of rb_p2p_export_local_inputs
+ *   acked           int32 [P][S]: rb_parse_datagrams_all's in/out tensor
+ *   lengths         int32 [P][S], optional: rb_encode_input_packets_all's output
+ *   reports         [RB_P2P_REPORTS_PER_TAKE][S], optional:
+ *                   rb_build_datagrams_all's tensor, read once per session
+ * Outputs, each written for every endpoint served:
+ *   input_lengths   int32 [P][S] = lengths where an Input is due, else 0: hand
+ *                   it to rb_build_datagrams_all as lengths
+ *   ack_due, reply_due, report_due, keepalive_due  uint8 [P][S]: that call's
+ *                   ack_owed / reply_owed / report_due / keepalive_due
+ *   sync_datagrams  uint8 [sync_slots][P*S][stride], sync_lengths int32
+ *                   [sync_slots][P][S] (10 or 0), sync_counts int32 [P][S]: the
+ *                   SyncRequests and SyncReplies, in rb_build_datagrams_all's
+ *                   layout with the same stride (bytes past the length are zero
+ *                   up to byte 15; rows at and above the count are untouched)
+ *   events          uint8 [P][S] RB_EP_EVENT_*; several Synchronizing events of
+ *                   one call fold into one bit with the newest count
+ *   sync_count      int32 [P][S] = NUM_SYNC_PACKETS - sync_remaining after the call
+ *   liveness_received  uint8 [P][S], optional = received | (ep_state != RUNNING)
+ *                   after the call: rb_p2p_poll_liveness's `received`.  poll's
+ *                   receive timers run in Running only (:360, :377-394), so an
+ *                   endpoint in any other state never ages
+ *   send_queue_len  int32 [P][S], optional = pending_output.len() (:296) =
+ *                   max(0, newest - acked); acked RB_NULL_FRAME counts from frame 0
+ *   session_running uint8 [S], optional = 1 where every endpoint of the mask
+ *                   is_synchronized() (:307-311; p2p_session.rs:598-618): the
+ *                   run mask rb_p2p_run_ticks_paced takes
+ *   status          int32 [P][S]: RB_DG_NO_ROOM where a sync message found no slot
+ *
+ * Per endpoint and call, in this order:
+ *  1. SHUTDOWN: nothing is read, every send output, events, sync_count,
+ *     send_queue_len and status is 0, liveness_received 1, the state untouched
+ *     (:429-432, :546-548).
+ *  2. disconnected set while the state is neither DISCONNECTED nor SHUTDOWN: the
+ *     state becomes DISCONNECTED and shutdown_at = now + 5000 (:325-333).
+ *  3. start set while INITIALIZING is synchronize() (:335-341): SYNCHRONIZING,
+ *     sync_remaining = 5, stats_start = now, one SyncRequest.  last_send,
+ *     last_input_recv and last_quality_report are set to now; the reference
+ *     stamps them at construction (:226-260), a deviation of at most the gap
+ *     between construction and synchronize, as section 18 states for its own.
+ *  4. Every slot in slot order: a datagram with at least 10 bytes below
+ *     min(length, stride) and variant 0 or 1 that passes the magic filter
+ *     (remote_magic != 0 && magic != remote_magic drops it, :551, with the value
+ *     as earlier slots of this call left it).  SyncRequest{x} queues
+ *     SyncReply{x} in any state (:578-583).  SyncReply{x} is on_sync_reply
+ *     (:586-614): ignored unless SYNCHRONIZING and x is outstanding; else the
+ *     nonce leaves and sync_remaining -= 1; above 0 that raises events bit 0
+ *     and sends another SyncRequest, at 0 the state becomes RUNNING, events bit
+ *     1 is raised and remote_magic takes the datagram's magic.
+ *  5. ack_owed sets ack_due and last_input_recv = now (:654, :682); reply_owed
+ *     sets reply_due (:697-701).
+ *  6. poll's timers (:351-404), all strict `<` in 64 bits.  SYNCHRONIZING:
+ *     last_send + 200 < now sends a SyncRequest.  RUNNING: last_input_recv + 200
+ *     < now sets the stamp to now, and an Input is due if newest > acked
+ *     (pending_output has a front, :468-471); last_quality_report + 200 < now
+ *     sets report_due and the stamp.  DISCONNECTED: shutdown_at < now makes the
+ *     state SHUTDOWN, and every send output of this call is 0 and nothing is
+ *     counted: the queue is drained before the socket sees it (:429-432).
+ *     queue_message stamps last_send_time at once (:533), so last_send reads as
+ *     now wherever this call already declared a message due.
+ *  7. The frame's own sends.  In RUNNING only (:444-446) newest above the last
+ *     frame sent makes an Input due; in every state last_newest follows newest,
+ *     so an input that arrived while the endpoint was not running is not sent
+ *     late on its own: it travels with the resend timer or the next frame.  One
+ *     Input is one message however many reasons it has.  Each entry of reports
+ *     whose frame is not RB_NULL_FRAME counts as one message (:736-742).
+ *  8. KeepAlive (:372-375): RUNNING, nothing declared due in steps 3-7 and
+ *     last_send + 200 < now.  One call folds one poll_remote_clients and the
+ *     frame's sends that follow it, so a KeepAlive the reference would queue
+ *     just ahead of an Input of the same iteration is not sent:
+ *     rb_build_datagrams_all's rule 6.
+ *  9. packets_sent rises by the messages declared due, sync messages included;
+ *     above 0, last_send = now (:527-538).  A sync message that finds no slot
+ *     is not sent and not counted, a request's nonce is not recorded, and
+ *     RB_DG_NO_ROOM is set; the 200 ms retry repeats it.
+ * Sync messages leave in the order "replies and requests as handled, then the
+ * timer's request".  disconnect_requested is never set on an outgoing Input and
+ * has no output here: the reference cannot send it either, send_pending_output
+ * runs in Running only while the flag is state == Disconnected (:488).  The
+ * pending-output overflow disconnect (:461-463) and spectator endpoints are out
+ * of scope.  kbps_sent (:279-301) adds size_of_val(&msg), a constant of the
+ * reference's build, per message; the caller computes
+ * ((packets_sent * (message_bytes + 28)) / seconds) / 1024 with seconds =
+ * (now - stats_start) / 1000 from the two state rows, NotSynchronized where
+ * seconds == 0 or the state is neither SYNCHRONIZING nor RUNNING.
+ *
+ * RB_INVALID_REQUEST, with nothing launched and no tensor touched: an empty mask
+ * or bits at or above num_players; num_players > 4; slots or sync_slots outside
+ * 1..RB_DG_MAX_SLOTS; a stride that breaks the rule above or is beyond 1 MiB,
+ * or a misaligned
+ * datagrams / sync_datagrams pointer; now_ms < 0; a NULL pointer that is not
+ * optional. */
+typedef struct rb_endpoint_protocol {
+  /* state */
+  uint8_t* ep_state;
+  int32_t* sync_remaining;
+  uint32_t* sync_nonces;
+  uint8_t* sync_valid;
+  uint8_t* sync_next;
+  int64_t* stamps;
+  int64_t* packets_sent;
+  int32_t* last_newest;
+  uint16_t* remote_magic;
+  /* inputs */
+  int64_t now_ms;
+  const uint16_t* local_magic;
+  const uint8_t* start;
+  const uint8_t* datagrams;
+  int64_t stride;
+  int32_t slots;
+  int32_t sync_slots;
+  const int32_t* dg_lengths;
+  const uint32_t* nonces;
+  const uint8_t* disconnected;
+  const uint8_t* ack_owed;
+  const uint8_t* reply_owed;
+  const uint8_t* received;
+  const int32_t* newest;
+  const int32_t* acked;
+  const int32_t* lengths;
+  const rb_checksum_report* reports;
+  /* outputs */
+  int32_t* input_lengths;
+  uint8_t* ack_due;
+  uint8_t* reply_due;
+  uint8_t* report_due;
+  uint8_t* keepalive_due;
+  uint8_t* sync_datagrams;
+  int32_t* sync_lengths;
+  int32_t* sync_counts;
+  uint8_t* events;
+  int32_t* sync_count;
+  uint8_t* liveness_received;
+  int32_t* send_queue_len;
+  uint8_t* session_running;
+  int32_t* status;
+} rb_endpoint_protocol;
+rb_status rb_endpoint_protocol_poll_all(int32_t device, void* stream, uint32_t handle_mask, int32_t num_players,
+                                        int32_t num_sessions, const rb_endpoint_protocol* io);
 
 #ifdef __cplusplus
 } /* extern "C" */
