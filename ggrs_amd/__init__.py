@@ -29,7 +29,8 @@ from .p2p import P2PSession, PlayerType, synth_network  # noqa: F401
 from .spectator import SpectatorSession  # noqa: F401
 from .migrate import move_sessions  # noqa: F401
 from .delivery_ring import DeliveryRing  # noqa: F401
-from .wire import decode_packets, encode_packets  # noqa: F401
+from .wire import decode_packets, decode_packets_grouped, encode_packets, encode_packets_grouped  # noqa: F401
+from .endpoint_groups import EndpointGroups  # noqa: F401
 from .datagram import ParsedDatagrams, build_datagrams, parse_datagrams  # noqa: F401
 from .protocol import EndpointProtocol  # noqa: F401
 

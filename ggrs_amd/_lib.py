@@ -334,6 +334,10 @@ SIGNATURES = [
                                             _P, _I32, _I32, _P, _P]),
     ("rb_encode_input_packets_all", _I32, [_I32, _P, ctypes.c_uint32, _I32, _I32, _I32, _P, _I32, _I32, _I32, _P, _P, _P,
                                             ctypes.c_int64, _P, _P]),
+    ("rb_decode_input_packets_grouped", _I32, [_I32, _P, ctypes.c_uint32, _I32, _I32, _I32, _I32, _P, ctypes.c_int64, _P,
+                                                _P, _P, _I32, _I32, _P, _P]),
+    ("rb_encode_input_packets_grouped", _I32, [_I32, _P, ctypes.c_uint32, _I32, _I32, _I32, _P, _I32, _I32, _I32, _P, _P,
+                                                _P, ctypes.c_int64, _P, _P]),
     ("rb_parse_datagrams_all", _I32, [_I32, _P, ctypes.c_uint32, _I32, _I32, ctypes.POINTER(RbDatagramParse)]),
     ("rb_build_datagrams_all", _I32, [_I32, _P, ctypes.c_uint32, _I32, _I32, ctypes.POINTER(RbDatagramBuild)]),
     ("rb_endpoint_protocol_poll_all", _I32, [_I32, _P, ctypes.c_uint32, _I32, _I32, ctypes.POINTER(RbEndpointProtocol)]),

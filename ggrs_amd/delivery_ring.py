@@ -66,19 +66,32 @@ class DeliveryRing:
         last = torch.where(count > 0, first + count - 1, torch.full_like(first, L.RB_NULL_FRAME)).to(torch.int32)
         self.upto[int(handle)] = torch.maximum(self.upto[int(handle)], last)
 
-    def receive_packets(self, handle_mask: int, packets, lengths, start_frames, max_prediction: int, status=None):
+    def _groups(self, handle_mask, groups):
+        from .endpoint_groups import as_groups
+        g = as_groups(groups, self.num_players)
+        if handle_mask is not None and int(handle_mask) != g.lead_mask:
+            raise ValueError("with groups, handle_mask is omitted or the groups' lead mask")
+        return g
+
+    def receive_packets(self, handle_mask, packets, lengths, start_frames, max_prediction: int, status=None, groups=None):
         """UdpProtocol::on_input for every endpoint of the handles in handle_mask, in one launch
         (wire.decode_packets in ring mode): packets uint8 [P, S, stride], lengths and start_frames
         int32 [P, S].  New frames go to their slots and ``upto`` advances; a packet with more than R
         new frames is taken up to R of them (the sender, acked with ``upto``, sends the rest again).
         The batch must have consumed every frame up to ``upto`` before the call.  Returns the status
         tensor [P, S] (0 new inputs, 1 nothing new, -1 malformed, -2 a gap; rows outside the mask
-        are left alone).  Does not synchronise."""
-        from .wire import decode_packets
+        are left alone).  With `groups` (an EndpointGroups, or a sequence of handle sequences or
+        masks) every endpoint carries its group's handles in one stream (rb_decode_input_packets_grouped,
+        DESIGN.md section 21): the rows read are the leads', every member's inputs and ``upto`` row
+        are written, and handle_mask is None or the groups' lead mask.  Does not synchronise."""
+        from .wire import decode_packets, decode_packets_grouped
+        if groups is not None:
+            return decode_packets_grouped(self.inputs, self.upto, self._groups(handle_mask, groups), packets, lengths,
+                                          start_frames, max_prediction, status=status, ring_frames=self.ring_frames)
         return decode_packets(self.inputs, self.upto, handle_mask, packets, lengths, start_frames, max_prediction,
                               status=status, ring_frames=self.ring_frames)
 
-    def send_packets(self, handle_mask: int, newest, acked, first_frame: int, packets, lengths, start_frames) -> None:
+    def send_packets(self, handle_mask, newest, acked, first_frame: int, packets, lengths, start_frames, groups=None) -> None:
         """UdpProtocol::send_pending_output for every endpoint of the handles in handle_mask, in one
         launch (wire.encode_packets in ring mode), with this ring holding the sender's inputs (the
         tensor of export_local_inputs or export_confirmed_inputs): frames acked + 1 .. newest
@@ -86,8 +99,13 @@ class DeliveryRing:
         int32 [P, S] (`sent` of export_local_inputs; the receiver's ``upto`` as it came back).
         lengths: bytes, 0 nothing pending, -1 longer than the stride, -2 more than R frames from the
         ack to newest (the reference input is gone; the reference disconnects such an endpoint).
+        With `groups` the frames of every member of a group go into one packet in the lead's row
+        (rb_encode_input_packets_grouped); handle_mask is None or the groups' lead mask.
         Does not synchronise."""
-        from .wire import encode_packets
+        from .wire import encode_packets, encode_packets_grouped
+        if groups is not None:
+            return encode_packets_grouped(self.inputs, self._groups(handle_mask, groups), newest, acked, first_frame,
+                                          packets, lengths, start_frames, ring_frames=self.ring_frames)
         encode_packets(self.inputs, handle_mask, newest, acked, first_frame, packets, lengths, start_frames,
                        ring_frames=self.ring_frames)
 

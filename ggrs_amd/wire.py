@@ -67,3 +67,35 @@ def encode_packets(inputs, handle_mask: int, newest, acked, first_frame: int, pa
     _call(L.load().rb_encode_input_packets_all, inputs.device.index or 0, ctypes.c_void_p(stream), int(handle_mask), P, S,
           inputs.element_size(), _ptr(inputs), int(inputs.shape[0]), int(ring_frames), int(first_frame), _ptr(acked),
           _ptr(newest), _ptr(packets), stride, _ptr(lengths), _ptr(start_frames))
+
+
+def decode_packets_grouped(inputs, upto, groups, packets, lengths, start_frames, max_prediction: int,
+                           status=None, ring_frames: int = 0):
+    """decode_packets for endpoints that carry a group of handles in one stream (`groups`: an
+    EndpointGroups or what it takes; rb_decode_input_packets_grouped).  The
+    packet, length, start frame and status are the lead's rows; every member's column of `inputs`
+    and row of `upto` is written."""
+    import torch
+    from .endpoint_groups import as_groups
+    if status is None:
+        status = torch.zeros_like(upto)
+    P, S, stride = _check(inputs, 0, packets, (lengths, start_frames, upto, status))
+    stream = torch.cuda.current_stream(inputs.device).cuda_stream
+    _call(L.load().rb_decode_input_packets_grouped, inputs.device.index or 0, ctypes.c_void_p(stream),
+          as_groups(groups, P).packed, P, S, inputs.element_size(), int(max_prediction), _ptr(packets), stride,
+          _ptr(lengths), _ptr(start_frames), _ptr(inputs), int(inputs.shape[0]), int(ring_frames), _ptr(upto), _ptr(status))
+    return status
+
+
+def encode_packets_grouped(inputs, groups, newest, acked, first_frame: int, packets, lengths, start_frames,
+                           ring_frames: int = 0) -> None:
+    """encode_packets for endpoints that carry a group of handles in one stream: acked and newest
+    are the lead's rows, the frames come from every member's column, the packet goes to the lead's
+    row (rb_encode_input_packets_grouped)."""
+    import torch
+    from .endpoint_groups import as_groups
+    P, S, stride = _check(inputs, 0, packets, (lengths, start_frames, acked, newest))
+    stream = torch.cuda.current_stream(inputs.device).cuda_stream
+    _call(L.load().rb_encode_input_packets_grouped, inputs.device.index or 0, ctypes.c_void_p(stream),
+          as_groups(groups, P).packed, P, S, inputs.element_size(), _ptr(inputs), int(inputs.shape[0]), int(ring_frames),
+          int(first_frame), _ptr(acked), _ptr(newest), _ptr(packets), stride, _ptr(lengths), _ptr(start_frames))

@@ -1137,6 +1137,60 @@ rb_status rb_encode_input_packets_all(int32_t device, void* stream, uint32_t han
                                       const int32_t* newest, uint8_t* packets, int64_t packet_stride, int32_t* lengths,
                                       int32_t* start_frames);
 
+/* ---- The codec for endpoints that carry several handles in one stream
+ * (DESIGN.md section 21): a remote peer with more than one local player, and
+ * every spectator endpoint.  InputBytes::from_inputs (network/protocol.rs:61-79)
+ * concatenates the inputs of the endpoint's handles, ascending, into one byte
+ * string per frame; send_pending_output XOR-deltas and RLE-codes that string,
+ * and on_input's to_player_inputs (:81-93) splits it again.
+ * A group is a non-empty set of handles whose inputs travel so; its lead is its
+ * lowest handle.  The endpoint of a group in session s owns row lead*S + s of
+ * every [P][S] endpoint tensor (packets, lengths, start_frames, acked, newest,
+ * status), so the datagram, protocol and liveness calls serve it under a
+ * handle_mask of the leads.  A frame of a group of k handles is k*input_bytes
+ * bytes (1 to 16): member 0's input, then member 1's, and so on.
+ * group_masks: byte g is the handle mask of group g, 0 for no group; up to four
+ * groups in any order.
+ * Tensor layouts, the linear and ring modes, stride and alignment rules and
+ * stream ordering are those of the _all pair above.  Stateless like it.
+ * RB_INVALID_REQUEST, with nothing launched and no tensor touched: whatever the
+ * _all pair refuses; all four bytes zero; a bit at or above num_players; two
+ * groups sharing a handle.
+ * Addresses stay inside the tensors for any lengths, start_frames, upto, acked,
+ * newest and packet bytes; results are defined for frames below 2^30.
+ *
+ * Decode: lengths, start_frames, upto and the packet are read from the lead's
+ * row only.  The reference input is the members' inputs of frame start - 1 one
+ * after the other (zeroed where _all's is).  The checks and status codes are
+ * _all's, in its order (nothing / overlong / gap / stale reference / negative
+ * reference / linear range), and one more malformed packet: a stream that is
+ * not a whole number of frames of k*input_bytes bytes.  The packet is
+ * validated as a whole before the first store; every new frame then writes
+ * each member's column (the first R frames above upto, no slot twice).  When the
+ * packet was taken (status 0, or 1 because it held nothing new) the new
+ * watermark goes to the upto row of every member, so rb_p2p_run_ticks and
+ * rb_spectator_run_ticks read what they read today; otherwise no upto row is
+ * written.  status is written in the lead's row only.  No other row of any
+ * tensor is touched. */
+rb_status rb_decode_input_packets_grouped(int32_t device, void* stream, uint32_t group_masks, int32_t num_players,
+                                          int32_t num_sessions, int32_t input_bytes, int32_t max_prediction,
+                                          const uint8_t* packets, int64_t packet_stride, const int32_t* lengths,
+                                          const int32_t* start_frames, void* inputs, int32_t frames, int32_t ring_frames,
+                                          int32_t* upto, int32_t* status);
+
+/* Encode: acked and newest are read from the lead's row; frames acked + 1 ..
+ * newest (first_frame .. newest before any ack) from every member's column; the
+ * packet, its length and start frame go to the lead's row.  0, -1 and -2 mean
+ * what they mean in rb_encode_input_packets_all, and the segments are chosen as
+ * there: the bytes are the reference's encoding of the concatenated frames.
+ * A group of one handle writes, byte for byte, what _all writes for that
+ * handle. */
+rb_status rb_encode_input_packets_grouped(int32_t device, void* stream, uint32_t group_masks, int32_t num_players,
+                                          int32_t num_sessions, int32_t input_bytes, const void* inputs, int32_t frames,
+                                          int32_t ring_frames, int32_t first_frame, const int32_t* acked,
+                                          const int32_t* newest, uint8_t* packets, int64_t packet_stride,
+                                          int32_t* lengths, int32_t* start_frames);
+
 /* ---- GGRS's wire messages for every endpoint of a batch in one launch
  * (DESIGN.md section 19): the datagrams the reference puts on its socket,
  * Message { header: { magic }, body: MessageBody } under bincode::serialize
